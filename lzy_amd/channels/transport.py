@@ -140,6 +140,8 @@ def ipc_enabled() -> bool:
 # cast to a narrower wire dtype by the producer's cast kernel, halving (or
 # quartering) the bytes crossing xGMI, and cast back on the consumer.
 # Both sides derive the decision from (meta.dtype, config) — deterministic.
+# The plain fp8 casts are unscaled (small-magnitude tensors come back all
+# zero); the 8-bit format for real tensors is block-scaled "mxfp8" below.
 # ---------------------------------------------------------------------------
 
 _WIRE_DTYPES = {
@@ -170,6 +172,22 @@ def _should_wirecast(dtype: torch.dtype, numel: int, wire) -> bool:
         < torch.empty(0, dtype=dtype).element_size()
         and numel >= _WIRE_MIN_ELEMS
     )
+
+
+# "mxfp8" is not a torch dtype: block-scaled FP8 (channels/mxwire.py) packs
+# into a flat uint8 buffer, which every path carries — RCCL device, the
+# host-staged fallback and CPU tensors over gloo.
+_MX_WIRE = "mxfp8"
+
+
+def wire_cast_mx() -> bool:
+    from lzy_amd.config import get_config
+
+    return get_config().channel_wire_cast == _MX_WIRE
+
+
+def _should_mxcast(dtype: torch.dtype, numel: int, enabled: bool) -> bool:
+    return enabled and dtype in _WIRE_CASTABLE and numel >= _WIRE_MIN_ELEMS
 
 
 def _pack_contiguous(t: torch.Tensor) -> torch.Tensor:
@@ -241,6 +259,7 @@ class Transport:
 
         self._chunk_bytes = get_config().channel_chunk_mb << 20
         self._wire = wire_cast_dtype()
+        self._mx = wire_cast_mx()
 
     def _wire_allowed(self, producer_cuda: bool) -> bool:
         """May the configured wire dtype be used for this transfer?  The
@@ -301,7 +320,13 @@ class Transport:
             # sides derive it from (producer device, _cuda_p2p, config).
             # fp8 wire dtypes are RCCL-device-path only — gloo (CPU
             # tensors, host-staged fallback) cannot carry float8.
-            if self._wire_allowed(t.is_cuda) and _should_wirecast(
+            # mxfp8 packs to flat uint8 BEFORE host staging (a host-staged
+            # device tensor is packed by the kernel) and rides every path.
+            if _should_mxcast(t.dtype, t.numel(), self._mx):
+                from lzy_amd.channels import mxwire
+
+                t = mxwire.mx8_pack(t)
+            elif self._wire_allowed(t.is_cuda) and _should_wirecast(
                 t.dtype, t.numel(), self._wire
             ):
                 t = wire_pack(t, self._wire)  # cast kernel on device
@@ -351,12 +376,20 @@ class Transport:
             ) and _should_wirecast(dtype, numel, self._wire)
             if casted:
                 wire_dtype = self._wire
+            mx = _should_mxcast(dtype, numel, self._mx)
             dev = self._device if on_device else None
+            if mx:
+                from lzy_amd.channels import mxwire
+
+                wire_dtype = torch.uint8
+                wire_shape: Tuple[int, ...] = (mxwire.mx8_nbytes(numel),)
+            else:
+                wire_shape = meta.shape
             per = self._chunk_elems(
                 torch.empty(0, dtype=wire_dtype).element_size()
             )
             buf = into if into is not None else torch.empty(
-                meta.shape, dtype=wire_dtype, device=dev
+                wire_shape, dtype=wire_dtype, device=dev
             )
             if buf.numel() <= per and offset_chunks == 0:
                 chunks = [buf]
@@ -370,7 +403,9 @@ class Transport:
                 out = buf
                 if want_cuda and not on_device:
                     out = out.to(self._device, non_blocking=False)
-                if casted:
+                if mx:
+                    out = mxwire.mx8_unpack(out, meta.shape, dtype)
+                elif casted:
                     out = wire_unpack(out, dtype)
                 return out
 

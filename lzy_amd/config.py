@@ -45,7 +45,7 @@ class Config:
     # channels (reference: channel-manager + slots transports)
     channel_transport: str = "rccl"    # "rccl" | "ipc"
     channel_chunk_mb: int = 256        # chunk size for large-tensor transfers
-    channel_wire_cast: str = ""        # ""|fp16|bf16|fp8e4m3|fp8e5m2: lossy wire dtype
+    channel_wire_cast: str = ""        # ""|fp16|bf16|mxfp8|fp8e4m3|fp8e5m2: lossy wire format (8-bit: prefer mxfp8, block-scaled, every path; plain fp8 is unscaled, RCCL-only)
     stream_merge: bool = True          # fold pair_reduce trees into streamed plans
     stream_chunk_mb: int = 32          # chunk size for streamed tree plans (1 GiB shard -> 32 chunks; pipeline fill ~2 chunks per extra level)
     # HIP data-plane kernels

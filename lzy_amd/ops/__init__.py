@@ -21,6 +21,7 @@ _LIB_PATH = os.path.join(os.path.dirname(__file__), "libhipops.so")
 
 _lib: Optional[ctypes.CDLL] = None
 _load_error: Optional[str] = None
+_MX8 = False  # libhipops.so exports lz_mx8_pack / lz_mx8_unpack
 
 
 def _try_load() -> Optional[ctypes.CDLL]:
@@ -100,6 +101,24 @@ def _try_load() -> Optional[ctypes.CDLL]:
         ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
         ctypes.c_void_p,
     ]
+    # newer exports bind optionally: a stale libhipops.so without them must
+    # not take the ops above down with it (mx8_* then raise
+    # NativeExtensionMissing on use)
+    global _MX8
+    try:
+        lib.lz_mx8_pack.restype = ctypes.c_int
+        lib.lz_mx8_pack.argtypes = [
+            ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+            ctypes.c_void_p,
+        ]
+        lib.lz_mx8_unpack.restype = ctypes.c_int
+        lib.lz_mx8_unpack.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+            ctypes.c_void_p,
+        ]
+        _MX8 = True
+    except AttributeError:
+        _MX8 = False
     lib.lz_error_name.restype = ctypes.c_char_p
     lib.lz_error_name.argtypes = [ctypes.c_int]
     lib.lz_set_max_blocks.restype = None
@@ -180,6 +199,103 @@ def cast_copy(src, dst) -> None:
             ctypes.c_void_p(_current_stream_ptr()),
         )
     )
+
+
+def _require_mx8() -> ctypes.CDLL:
+    lib = _require_native()
+    if not _MX8:
+        raise NativeExtensionMissing(
+            f"{_LIB_PATH} is stale: it lacks lz_mx8_pack/lz_mx8_unpack; "
+            f"rebuild with `python setup.py build_ext --inplace --force`"
+        )
+    return lib
+
+
+def mx8_nbytes(numel: int) -> int:
+    """Wire bytes of ``numel`` elements in the block-scaled FP8 format:
+    32 e4m3 payload bytes + 1 scale byte per 32-element block."""
+    return 33 * ((int(numel) + 31) // 32)
+
+
+def _mx8_check_dtype(dtype, what: str) -> None:
+    import torch
+
+    if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f"{what}: dtype must be f32/bf16/f16, got {dtype}")
+
+
+def mx8_pack(t, out=None):
+    """Pack a device f32/bf16/f16 tensor into the block-scaled FP8 (MXFP8)
+    wire format (docs/mxwire.md): one fused amax-reduce + scale + e4m3
+    quantize pass on the current stream.  Returns a flat uint8 tensor of
+    ``mx8_nbytes(t.numel())`` bytes (``out`` when given)."""
+    import torch
+
+    if not t.is_cuda:
+        raise ValueError("mx8_pack requires a device tensor")
+    _mx8_check_dtype(t.dtype, "mx8_pack")
+    lib = _require_mx8()
+    s = t.detach().contiguous()
+    n = s.numel()
+    nbytes = mx8_nbytes(n)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+              and out.numel() == nbytes):
+        raise ValueError(
+            f"mx8_pack: out must be a contiguous device uint8[{nbytes}]"
+        )
+    _check(
+        lib.lz_mx8_pack(
+            ctypes.c_void_p(s.data_ptr()),
+            _dtype_code(s.dtype),
+            ctypes.c_void_p(out.data_ptr()),
+            n,
+            ctypes.c_void_p(_current_stream_ptr()),
+        )
+    )
+    return out
+
+
+def mx8_unpack(buf, numel_or_shape, dtype, out=None):
+    """Decode an MXFP8 wire buffer (device uint8) into a tensor of
+    ``dtype`` (f32/bf16/f16) and the given numel or shape."""
+    import torch
+
+    if isinstance(numel_or_shape, int):
+        shape = (numel_or_shape,)
+    else:
+        shape = tuple(int(d) for d in numel_or_shape)
+    n = 1
+    for d in shape:
+        n *= d
+    if not buf.is_cuda:
+        raise ValueError("mx8_unpack requires a device buffer")
+    _mx8_check_dtype(dtype, "mx8_unpack")
+    if buf.dtype != torch.uint8 or not buf.is_contiguous() \
+            or buf.numel() != mx8_nbytes(n):
+        raise ValueError(
+            f"mx8_unpack: buffer must be contiguous uint8[{mx8_nbytes(n)}] "
+            f"for {n} elements, got {buf.dtype}[{buf.numel()}]"
+        )
+    lib = _require_mx8()
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=buf.device)
+    elif not (out.is_cuda and out.dtype == dtype and out.is_contiguous()
+              and out.numel() == n):
+        raise ValueError(
+            f"mx8_unpack: out must be a contiguous device {dtype}[{n}]"
+        )
+    _check(
+        lib.lz_mx8_unpack(
+            ctypes.c_void_p(buf.data_ptr()),
+            ctypes.c_void_p(out.data_ptr()),
+            _dtype_code(dtype),
+            n,
+            ctypes.c_void_p(_current_stream_ptr()),
+        )
+    )
+    return out
 
 
 def device_checksum(t, method: str = "auto") -> int:

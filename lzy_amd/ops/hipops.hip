@@ -156,6 +156,303 @@ extern "C" hipError_t lz_cast_copy(const void* src, int src_dtype, void* dst,
 }
 
 // ---------------------------------------------------------------------------
+// mx8 pack/unpack: block-scaled FP8 wire format (OCP MXFP8, docs/mxwire.md).
+//
+// Every 32 elements share one power-of-two scale byte (E8M0); the payload
+// is one OCP e4m3fn byte per element.  Wire buffer for n elements, with
+// nblk = ceil(n/32): payload bytes [0, 32*nblk), then nblk scale bytes.
+// This is also the operand layout of gfx950's block-scaled MFMA.
+//
+// Work item = 8 consecutive elements ("group"): the 4 lanes of an aligned
+// quad own one block and a wave covers 16 blocks at a time.  The loop bound
+// is wave-uniform (every lane of a wave takes the same trips), so the
+// cross-lane steps always run with all 64 lanes; lanes past the end carry
+// zeros and store nothing.  The pack is VALU-bound before it is HBM-bound
+// (docs/performance.md), hence the packed converts and DPP moves.
+//
+// ALIGNED: src/dst allow 16 B (payload: 8 B) vector accesses.  Views that
+// are only element-aligned take the same kernel with per-element accesses.
+// ---------------------------------------------------------------------------
+
+struct alignas(16) LzVec16 { uint32_t w[4]; };
+struct alignas(8) LzVec8 { uint32_t w[2]; };
+
+// scale byte of a block from the raw bits of its finite amax (>= 0):
+// the smallest 2^(b-127) with amax / 2^(b-127) <= 448 = 1.75 * 2^8
+__device__ __forceinline__ uint32_t lz_mx8_scale_byte(uint32_t amax_bits) {
+    int e = (int)((amax_bits >> 23) & 0xffu);
+    int b = e - 8 + ((amax_bits & 0x7fffffu) > 0x600000u ? 1 : 0);
+    return (uint32_t)(b < 0 ? 0 : b);
+}
+
+// x * 2^(127-b), clamped to the e4m3 finite range, NaN kept.  The multiply
+// is exact (power of two) and finite values never exceed 448 by the choice
+// of b, so the explicit clamp only ever moves +-Inf.  med3 drops NaN, the
+// select puts it back as the one canonical quiet NaN (wire byte 0x7f).
+__device__ __forceinline__ float lz_mx8_scaled(float x, float mult) {
+    const float v = x * mult;
+    const float c = __builtin_amdgcn_fmed3f(v, -448.f, 448.f);
+    return (v != v) ? __uint_as_float(0x7fc00000u) : c;
+}
+
+// 4 floats -> 4 e4m3 bytes (byte k = element k), RNE: v_cvt_pk_fp8_f32, the
+// hardware convert behind __hip_fp8_e4m3 (OCP e4m3fn on gfx950), two
+// elements per instruction, written straight into the half-words of a dword
+__device__ __forceinline__ uint32_t lz_mx8_encode4(const float* f, float mult) {
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(lz_mx8_scaled(f[0], mult),
+                                            lz_mx8_scaled(f[1], mult), 0, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(lz_mx8_scaled(f[2], mult),
+                                        lz_mx8_scaled(f[3], mult), w, true);
+    return (uint32_t)w;
+}
+
+// a lane's 8 elements as fp32.  FULL: all 8 lie inside [0, n) and src + e0
+// is 16 B-aligned (one or two 16 B loads); otherwise guarded, zeros past n.
+template <typename T, bool FULL>
+__device__ __forceinline__ void lz_mx8_load(const T* __restrict__ src, int64_t e0,
+                                            int64_t n, float (&f)[8]) {
+    constexpr int V = 8;
+    T x[V];
+    if (FULL) {
+        LzVec16 q[sizeof(T) * V / 16];
+        const LzVec16* p = reinterpret_cast<const LzVec16*>(src + e0);
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(T) * V / 16); ++k) q[k] = p[k];
+        __builtin_memcpy(x, q, sizeof(x));
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            x[k] = (e0 + k < n) ? src[e0 + k] : lz_from_float<T>(0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) f[k] = lz_to_float<T>(x[k]);
+}
+
+// DPP lane moves (VALU, no LDS round trip).  Must run with all 64 lanes on.
+// quad_perm:[a,b,c,d] = a | b<<2 | c<<4 | d<<6: lane i of a quad reads lane sel[i]
+#define LZ_DPP_QUAD_XOR1 0xB1  // [1,0,3,2]
+#define LZ_DPP_QUAD_XOR2 0x4E  // [2,3,0,1]
+#define LZ_DPP_ROW_SHL(k) (0x100 + (k))  // lane i reads lane i+k of its 16-lane row
+template <int CTRL>
+__device__ __forceinline__ uint32_t lz_dpp(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
+}
+
+// quantize and store one group (8 elements of lane `lane`, group g); every
+// lane of the wave calls this together.  FULL: all 64 groups of the wave
+// are inside the tensor, no guards.
+template <bool ALIGNED, bool FULL>
+__device__ __forceinline__ void lz_mx8_emit(const float (&f)[8], int64_t g, int lane,
+                                            int64_t ngroups, int64_t nblk,
+                                            uint8_t* __restrict__ dst,
+                                            uint8_t* __restrict__ scales) {
+    // amax over the finite elements on raw bits (integer order == float
+    // order for |x|).  Biased by one exponent step: Inf/NaN (exponent 255)
+    // carry into the sign bit and lose every signed max.
+    int32_t tmax = 0x00800000;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        int32_t t = (int32_t)((__float_as_uint(f[k]) & 0x7fffffffu) + 0x00800000u);
+        tmax = t > tmax ? t : tmax;
+    }
+    uint32_t amax = (uint32_t)tmax - 0x00800000u;
+    // quad reduce: the 4 lanes of a block
+    uint32_t o = lz_dpp<LZ_DPP_QUAD_XOR1>(amax);
+    amax = o > amax ? o : amax;
+    o = lz_dpp<LZ_DPP_QUAD_XOR2>(amax);
+    amax = o > amax ? o : amax;
+
+    const uint32_t b = lz_mx8_scale_byte(amax);
+    const float mult = __uint_as_float((254u - b) << 23);
+    const uint32_t lo = lz_mx8_encode4(&f[0], mult);
+    const uint32_t hi = lz_mx8_encode4(&f[4], mult);
+    // gather the 4 scale bytes of each 16-lane row into its first lane, so
+    // a wave's 16 scale bytes leave as 4 adjacent dword stores
+    uint32_t sw = b;
+    sw |= lz_dpp<LZ_DPP_ROW_SHL(4)>(b) << 8;
+    sw |= lz_dpp<LZ_DPP_ROW_SHL(8)>(b) << 16;
+    sw |= lz_dpp<LZ_DPP_ROW_SHL(12)>(b) << 24;
+
+    if (FULL || g < ngroups) {
+        const int64_t e0 = g * 8;
+        if (ALIGNED) {
+            LzVec8 pv;
+            pv.w[0] = lo;
+            pv.w[1] = hi;
+            *reinterpret_cast<LzVec8*>(dst + e0) = pv;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                dst[e0 + k] = (uint8_t)(lo >> (8 * k));
+                dst[e0 + 4 + k] = (uint8_t)(hi >> (8 * k));
+            }
+        }
+        if ((lane & 15) == 0) {
+            const int64_t blk = g >> 2;  // multiple of 4
+            if (ALIGNED && (FULL || blk + 4 <= nblk)) {
+                *reinterpret_cast<uint32_t*>(scales + blk) = sw;
+            } else {
+                for (int k = 0; k < 4 && blk + k < nblk; ++k)
+                    scales[blk + k] = (uint8_t)(sw >> (8 * k));
+            }
+        }
+    }
+}
+
+template <typename T, bool ALIGNED>
+__global__ void __launch_bounds__(LZ_BLOCK)
+mx8_pack_kernel(const T* __restrict__ src, uint8_t* __restrict__ dst, int64_t n) {
+    const int64_t nblk = (n + 31) >> 5;
+    const int64_t ngroups = nblk * 4;
+    uint8_t* __restrict__ scales = dst + nblk * 32;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+
+    // g0, the group of the wave's lane 0, and every branch on it are
+    // wave-uniform: the cross-lane steps always run with all 64 lanes.
+    // Two groups per trip: on the unguarded fast path both 16 B loads issue
+    // before either is consumed.  The guarded path takes the tail and
+    // element-aligned tensors.
+    for (int64_t g0 = (int64_t)blockIdx.x * blockDim.x + wave * 64; g0 < ngroups;
+         g0 += 2 * stride) {
+        const int64_t ga = g0 + lane, gb = ga + stride;
+        float fa[8], fb[8];
+        if (ALIGNED && (g0 + stride + 64) * 8 <= n) {
+            lz_mx8_load<T, true>(src, ga * 8, n, fa);
+            lz_mx8_load<T, true>(src, gb * 8, n, fb);
+            lz_mx8_emit<true, true>(fa, ga, lane, ngroups, nblk, dst, scales);
+            lz_mx8_emit<true, true>(fb, gb, lane, ngroups, nblk, dst, scales);
+        } else {
+            const bool two = g0 + stride < ngroups;
+            lz_mx8_load<T, false>(src, ga * 8, n, fa);
+            lz_mx8_emit<ALIGNED, false>(fa, ga, lane, ngroups, nblk, dst, scales);
+            if (two) {
+                lz_mx8_load<T, false>(src, gb * 8, n, fb);
+                lz_mx8_emit<ALIGNED, false>(fb, gb, lane, ngroups, nblk, dst, scales);
+            }
+        }
+    }
+}
+
+template <typename T, bool ALIGNED>
+__global__ void __launch_bounds__(LZ_BLOCK)
+mx8_unpack_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst, int64_t n) {
+    constexpr int V = 8;
+    const int64_t nblk = (n + 31) >> 5;
+    const int64_t ngroups = nblk * 4;
+    const uint8_t* __restrict__ scales = src + nblk * 32;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups;
+         g += stride) {
+        const int64_t e0 = g * V;
+        if (e0 >= n) continue;  // padded tail of the last block
+        uint32_t w[2];
+        if (ALIGNED) {
+            LzVec8 pv = *reinterpret_cast<const LzVec8*>(src + e0);
+            w[0] = pv.w[0];
+            w[1] = pv.w[1];
+        } else {
+            w[0] = w[1] = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                w[0] |= (uint32_t)src[e0 + k] << (8 * k);
+                w[1] |= (uint32_t)src[e0 + 4 + k] << (8 * k);
+            }
+        }
+        const uint32_t b = scales[g >> 2];
+        const float mult = __uint_as_float(b ? (b << 23) : 0x00400000u);
+        T y[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            __hip_fp8_e4m3 q;
+            q.__x = (__hip_fp8_storage_t)(w[k >> 2] >> (8 * (k & 3)));
+            y[k] = lz_from_float<T>(float(q) * mult);
+        }
+        if (ALIGNED && e0 + V <= n) {
+            LzVec16 q[sizeof(T) * V / 16];
+            __builtin_memcpy(q, y, sizeof(y));
+            LzVec16* p = reinterpret_cast<LzVec16*>(dst + e0);
+#pragma unroll
+            for (int k = 0; k < (int)(sizeof(T) * V / 16); ++k) p[k] = q[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < V; ++k)
+                if (e0 + k < n) dst[e0 + k] = y[k];
+        }
+    }
+}
+
+static inline int lz_mx8_grid(int64_t n) {
+    int64_t ngroups = ((n + 31) >> 5) * 4;
+    int64_t want = (ngroups + LZ_BLOCK - 1) / LZ_BLOCK;
+    return (int)(want < 1 ? 1 : (want > g_max_blocks ? g_max_blocks : want));
+}
+
+// src: n elements of src_dtype (f32/f16/bf16); dst_u8: 33*ceil(n/32) bytes
+extern "C" hipError_t lz_mx8_pack(const void* src, int src_dtype, void* dst_u8,
+                                  int64_t n, void* stream) {
+    if (src_dtype != LZ_F32 && src_dtype != LZ_F16 && src_dtype != LZ_BF16)
+        return hipErrorInvalidValue;
+    if (n < 0) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    const int blocks = lz_mx8_grid(n);
+    const bool aligned = (((uintptr_t)src & 15) == 0) && (((uintptr_t)dst_u8 & 7) == 0);
+#define LZ_MXP_CASE(code, T)                                                    \
+    case code:                                                                  \
+        if (aligned)                                                            \
+            hipLaunchKernelGGL((mx8_pack_kernel<T, true>), dim3(blocks),        \
+                               dim3(LZ_BLOCK), 0, s, (const T*)src,             \
+                               (uint8_t*)dst_u8, n);                            \
+        else                                                                    \
+            hipLaunchKernelGGL((mx8_pack_kernel<T, false>), dim3(blocks),       \
+                               dim3(LZ_BLOCK), 0, s, (const T*)src,             \
+                               (uint8_t*)dst_u8, n);                            \
+        break;
+    switch (src_dtype) {
+        LZ_MXP_CASE(LZ_F32, float)
+        LZ_MXP_CASE(LZ_F16, __half)
+        LZ_MXP_CASE(LZ_BF16, __hip_bfloat16)
+        default: return hipErrorInvalidValue;
+    }
+#undef LZ_MXP_CASE
+    return hipGetLastError();
+}
+
+// src_u8: 33*ceil(n/32) bytes; dst: n elements of dst_dtype (f32/f16/bf16)
+extern "C" hipError_t lz_mx8_unpack(const void* src_u8, void* dst, int dst_dtype,
+                                    int64_t n, void* stream) {
+    if (dst_dtype != LZ_F32 && dst_dtype != LZ_F16 && dst_dtype != LZ_BF16)
+        return hipErrorInvalidValue;
+    if (n < 0) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    const int blocks = lz_mx8_grid(n);
+    const bool aligned = (((uintptr_t)src_u8 & 7) == 0) && (((uintptr_t)dst & 15) == 0);
+#define LZ_MXU_CASE(code, T)                                                    \
+    case code:                                                                  \
+        if (aligned)                                                            \
+            hipLaunchKernelGGL((mx8_unpack_kernel<T, true>), dim3(blocks),      \
+                               dim3(LZ_BLOCK), 0, s, (const uint8_t*)src_u8,    \
+                               (T*)dst, n);                                     \
+        else                                                                    \
+            hipLaunchKernelGGL((mx8_unpack_kernel<T, false>), dim3(blocks),     \
+                               dim3(LZ_BLOCK), 0, s, (const uint8_t*)src_u8,    \
+                               (T*)dst, n);                                     \
+        break;
+    switch (dst_dtype) {
+        LZ_MXU_CASE(LZ_F32, float)
+        LZ_MXU_CASE(LZ_F16, __half)
+        LZ_MXU_CASE(LZ_BF16, __hip_bfloat16)
+        default: return hipErrorInvalidValue;
+    }
+#undef LZ_MXU_CASE
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // checksum: 64-bit content hash of a device buffer.
 // ---------------------------------------------------------------------------
 
