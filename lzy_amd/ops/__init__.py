@@ -177,17 +177,36 @@ def _current_stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _check_dst(op: str, dst, numel: int, shape=None) -> None:
+    """The kernels write ``numel`` elements linearly from ``dst.data_ptr()``:
+    anything but a contiguous device tensor of exactly that size would be
+    written out of order or out of bounds, so it is rejected up front."""
+    if not dst.is_cuda:
+        raise ValueError(f"{op}: dst must be a device tensor")
+    if not dst.is_contiguous():
+        raise ValueError(f"{op}: dst must be contiguous")
+    if dst.numel() != numel:
+        raise ValueError(
+            f"{op}: dst has {dst.numel()} elements, expected {numel}"
+        )
+    if shape is not None and tuple(dst.shape) != tuple(shape):
+        raise ValueError(
+            f"{op}: dst has shape {tuple(dst.shape)}, expected {tuple(shape)}"
+        )
+
+
 def cast_copy(src, dst) -> None:
-    """dst[i] = cast(src[i]); both device-contiguous, same numel.
+    """dst[i] = cast(src[i]); dst device-contiguous, same numel.
 
     Fused pack+dtype-cast on the current stream — the channel transport's
-    cast-on-the-wire primitive.
+    cast-on-the-wire primitive.  Numeric contract: docs/api.md.
     """
     lib = _require_native()
     if src.numel() != dst.numel():
         raise ValueError("cast_copy: numel mismatch")
     if not (src.is_cuda and dst.is_cuda):
         raise ValueError("cast_copy: device tensors required")
+    _check_dst("cast_copy", dst, src.numel())
     s = src.detach().contiguous()
     _check(
         lib.lz_cast_copy(
@@ -408,6 +427,8 @@ def normalize(src, dst=None, eps: float = 1e-6):
     s = src.detach().contiguous()
     if dst is None:
         dst = torch.empty_like(s)
+    else:
+        _check_dst("normalize", dst, s.numel())
     st = stats(s, use_abs=False)
     _check(
         lib.lz_normalize_apply(
@@ -435,6 +456,8 @@ def scale_shift(src, a: float, b: float, dst=None):
     s = src.detach().contiguous()
     if dst is None:
         dst = torch.empty_like(s)
+    else:
+        _check_dst("scale_shift", dst, s.numel())
     _check(
         lib.lz_scale_shift(
             ctypes.c_void_p(s.data_ptr()),
@@ -464,6 +487,8 @@ def axpby(a, b, alpha: float = 1.0, beta: float = 1.0, dst=None):
     y = b.detach().contiguous()
     if dst is None:
         dst = torch.empty_like(x)
+    else:
+        _check_dst("axpby", dst, x.numel())
     _check(
         lib.lz_axpby(
             ctypes.c_void_p(x.data_ptr()),
@@ -494,6 +519,8 @@ def transpose_cast(src, dst=None, dtype=None):
     out_dtype = dtype or s.dtype
     if dst is None:
         dst = torch.empty(cols, rows, dtype=out_dtype, device=s.device)
+    else:
+        _check_dst("transpose_cast", dst, rows * cols, shape=(cols, rows))
     _check(
         lib.lz_transpose_cast(
             ctypes.c_void_p(s.data_ptr()),
@@ -513,9 +540,17 @@ def fill_pattern(t, seed: int = 0, mask16: int = 0) -> None:
 
     ``mask16``: AND every 16-bit lane with this mask in the same pass —
     e.g. 0x3FFF makes a bf16 buffer finite positive synthetic data
-    without a second read+write over HBM."""
+    without a second read+write over HBM.
+
+    Byte ``8*i + k`` is byte ``k`` of ``splitmix64(seed ^ i) & mask``,
+    trailing ``nbytes % 8`` bytes included.  ``t`` is written in place, so
+    it must be a contiguous device tensor."""
     lib = _require_native()
-    flat = t.detach().contiguous()
+    if not t.is_cuda:
+        raise ValueError("fill_pattern requires a device tensor")
+    if not t.is_contiguous():
+        raise ValueError("fill_pattern: tensor must be contiguous")
+    flat = t.detach()
     nbytes = flat.numel() * flat.element_size()
     if mask16:
         _check(

@@ -23,6 +23,7 @@
 #include <hip/hip_fp8.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #define LZ_BLOCK 256
 // Default grid cap: 4 workgroups per CU.  Swept on MI355X (profiles/
@@ -79,6 +80,24 @@ template <> __device__ __forceinline__ int32_t lz_from_float<int32_t>(float v) {
 template <> __device__ __forceinline__ int64_t lz_from_float<int64_t>(float v) { return (int64_t)v; }
 template <> __device__ __forceinline__ double lz_from_float<double>(float v) { return (double)v; }
 
+// One element of cast_copy.  Pairs of plain arithmetic types (f32, f64, i32,
+// i64, u8) convert directly, so i32/i64/f64 keep every bit the destination
+// can hold; any pair with a 16- or 8-bit float goes through f32, the only
+// conversion those types have (f64 -> bf16 is therefore double-rounded).
+template <typename T>
+inline constexpr bool lz_is_plain =
+    std::is_same<T, float>::value || std::is_same<T, double>::value ||
+    std::is_same<T, int32_t>::value || std::is_same<T, int64_t>::value ||
+    std::is_same<T, uint8_t>::value;
+
+template <typename SrcT, typename DstT>
+__device__ __forceinline__ DstT lz_convert(SrcT v) {
+    if constexpr (lz_is_plain<SrcT> && lz_is_plain<DstT>)
+        return static_cast<DstT>(v);
+    else
+        return lz_from_float<DstT>(lz_to_float<SrcT>(v));
+}
+
 // Vectorized cast: each lane handles 8 contiguous elements per iteration
 // (G13: hipcc does not auto-vectorize half-width loads; short4/short8
 // reinterpret is the coalescing sweet spot).
@@ -99,14 +118,14 @@ __global__ void cast_copy_kernel(const SrcT* __restrict__ src,
         SrcV s = srcv[i];
         DstV d;
 #pragma unroll
-        for (int k = 0; k < V; ++k) d.v[k] = lz_from_float<DstT>(lz_to_float<SrcT>(s.v[k]));
+        for (int k = 0; k < V; ++k) d.v[k] = lz_convert<SrcT, DstT>(s.v[k]);
         dstv[i] = d;
     }
     // tail
     int64_t tail_start = vec_n * V;
     for (int64_t i = tail_start + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
          i < n; i += stride) {
-        dst[i] = lz_from_float<DstT>(lz_to_float<SrcT>(src[i]));
+        dst[i] = lz_convert<SrcT, DstT>(src[i]);
     }
 }
 
@@ -737,9 +756,13 @@ __global__ void normalize_apply_kernel(const SrcT* __restrict__ src,
                                        DstT* __restrict__ dst, int64_t n,
                                        const double* __restrict__ stats,
                                        float eps) {
-    const float mean = (float)(stats[0] / (double)n);
-    const float var = (float)(stats[1] / (double)n) - mean * mean;
-    const float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
+    // mean/var/rstd in double, as mean_std() forms them on the host: in f32
+    // the S2/n - mean^2 cancellation loses rstd once |mean| >> std.  Once
+    // per thread; only the per-element arithmetic below runs in f32.
+    const double mean_d = stats[0] / (double)n;
+    const double var_d = stats[1] / (double)n - mean_d * mean_d;
+    const float mean = (float)mean_d;
+    const float rstd = (float)(1.0 / sqrt(fmax(var_d, 0.0) + (double)eps));
 
     constexpr int V = 8;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -1164,36 +1187,46 @@ extern "C" hipError_t lz_transpose_cast(const void* src, int src_dtype,
 // (fused here: a separate torch bitwise_and_ pass costs 2x the buffer in
 // HBM traffic — measured 389 us per 1 GiB shard, profiles/
 // kernel_stats_bench_fused.md).
-__global__ void fill_pattern_kernel(uint64_t* __restrict__ data, int64_t nwords,
+__global__ void fill_pattern_kernel(uint8_t* __restrict__ bytes, int64_t nbytes,
                                     uint64_t seed, uint64_t mask16) {
+    uint64_t* __restrict__ data = reinterpret_cast<uint64_t*>(bytes);
+    const int64_t nwords = nbytes >> 3;
     int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const uint64_t m = mask16 ? (mask16 * 0x0001000100010001ULL) : ~0ULL;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords;
          i += stride) {
         data[i] = splitmix64(seed ^ (uint64_t)i) & m;
     }
+    // trailing nbytes % 8 bytes: the low bytes of word `nwords`, one thread
+    const int tail = (int)(nbytes & 7);
+    if (tail && blockIdx.x == 0 && threadIdx.x == 0) {
+        const uint64_t w = splitmix64(seed ^ (uint64_t)nwords) & m;
+        uint8_t* p = bytes + (nwords << 3);
+        for (int k = 0; k < tail; ++k) p[k] = (uint8_t)(w >> (8 * k));
+    }
 }
 
-extern "C" hipError_t lz_fill_pattern(void* data, int64_t nbytes, uint64_t seed,
-                                      void* stream) {
+static hipError_t lz_fill_launch(void* data, int64_t nbytes, uint64_t seed,
+                                 uint64_t mask16, void* stream) {
+    if (nbytes < 0) return hipErrorInvalidValue;
+    if (nbytes == 0) return hipSuccess;
     int64_t nwords = nbytes >> 3;
     int64_t want = (nwords + LZ_BLOCK - 1) / LZ_BLOCK;
     int blocks = (int)(want < 1 ? 1 : (want > g_max_blocks ? g_max_blocks : want));
     hipLaunchKernelGGL(fill_pattern_kernel, dim3(blocks), dim3(LZ_BLOCK), 0,
-                       (hipStream_t)stream, (uint64_t*)data, nwords, seed, 0ULL);
+                       (hipStream_t)stream, (uint8_t*)data, nbytes, seed, mask16);
     return hipGetLastError();
+}
+
+extern "C" hipError_t lz_fill_pattern(void* data, int64_t nbytes, uint64_t seed,
+                                      void* stream) {
+    return lz_fill_launch(data, nbytes, seed, 0ULL, stream);
 }
 
 extern "C" hipError_t lz_fill_pattern_masked(void* data, int64_t nbytes,
                                              uint64_t seed, uint64_t mask16,
                                              void* stream) {
-    int64_t nwords = nbytes >> 3;
-    int64_t want = (nwords + LZ_BLOCK - 1) / LZ_BLOCK;
-    int blocks = (int)(want < 1 ? 1 : (want > g_max_blocks ? g_max_blocks : want));
-    hipLaunchKernelGGL(fill_pattern_kernel, dim3(blocks), dim3(LZ_BLOCK), 0,
-                       (hipStream_t)stream, (uint64_t*)data, nwords, seed,
-                       mask16 & 0xFFFFULL);
-    return hipGetLastError();
+    return lz_fill_launch(data, nbytes, seed, mask16 & 0xFFFFULL, stream);
 }
 
 extern "C" const char* lz_error_name(hipError_t err) { return hipGetErrorName(err); }

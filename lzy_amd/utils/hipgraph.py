@@ -41,7 +41,8 @@ class StepGraph:
         """Input refresh before replay.  torch's same-dtype D2D ``copy_``
         runs the byte-wise rocclr copyBuffer (~1.4 TB/s measured); the
         vectorized cast_copy kernel streams at ~5.5 TB/s."""
-        if dst.is_cuda and src.is_cuda and src.is_contiguous():
+        if dst.is_cuda and src.is_cuda and src.is_contiguous() \
+                and dst.is_contiguous():
             try:
                 from lzy_amd import ops
 
