@@ -12,6 +12,17 @@ Each call is timed with device events; the figure reported is
 (bytes read + bytes written) / median time.  Also reports the fraction of
 payload bytes on which the kernel and the torch codec disagree, over a
 1M-element sample.  Prints one JSON line last.
+
+``--mode axpby`` times the fused decode-combine of a wired merge-tree edge
+against the two-kernel sequence it replaces, on the same buffers, for bf16
+and f32 accumulators of ``--melems`` Mi elements (default 64), alternating
+the two in one process:
+
+  * fused     ops.mx8_axpby(a, wire, dst=out)           2+33/32 B read, 2 B written (bf16)
+  * sequence  ops.mx8_unpack(wire -> tmp); ops.axpby(a, tmp, dst=out)
+                                                        33/32+4 B read, 4 B written (bf16)
+
+and checks that both give the same values to one unit in the last place.
 """
 import argparse
 import json
@@ -26,8 +37,90 @@ import lzy_amd.ops as ops
 from lzy_amd.channels.mxwire import mx8_pack_torch
 
 
+def _time_alternating(cases, iters, warmup):
+    """Median/min/max seconds per case, cases alternated round-robin and
+    each call bracketed by device events."""
+    for _ in range(warmup):
+        for fn in cases.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in cases}
+    for _ in range(iters):
+        for name, fn in cases.items():
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            times[name].append(e0.elapsed_time(e1) * 1e-3)
+    return {k: sorted(v) for k, v in times.items()}
+
+
+def axpby_mode(args) -> None:
+    n = args.melems << 20
+    alpha, beta = 0.5, 0.5
+    wire = torch.empty(ops.mx8_nbytes(n), device="cuda", dtype=torch.uint8)
+    src = torch.empty(n, device="cuda", dtype=torch.bfloat16)
+    ops.fill_pattern(src, seed=3, mask16=0x3FFF)  # finite positive bf16
+    ops.mx8_pack(src, out=wire)
+    del src
+    result = {"mode": "axpby", "melems": args.melems, "iters": args.iters}
+    for dtype, name in ((torch.bfloat16, "bf16"), (torch.float32, "f32")):
+        es = 2 if dtype == torch.bfloat16 else 4
+        torch.manual_seed(5)
+        a = (torch.rand(n, device="cuda") + 0.5).to(dtype)  # positive, like the wire
+        out_f = torch.empty_like(a)
+        out_s = torch.empty_like(a)
+        tmp = torch.empty_like(a)
+
+        def fused():
+            ops.mx8_axpby(a, wire, alpha, beta, dst=out_f)
+
+        def sequence():
+            ops.mx8_unpack(wire, n, dtype, out=tmp)
+            ops.axpby(a, tmp, alpha, beta, dst=out_s)
+
+        ts = _time_alternating({"fused": fused, "sequence": sequence},
+                               args.iters, args.warmup)
+        nbytes = {"fused": n * es + wire.numel() + n * es,
+                  "sequence": wire.numel() + n * es + 2 * n * es + n * es}
+        entry = {}
+        for k, t in ts.items():
+            med = statistics.median(t)
+            entry[k] = {
+                "median_us": round(med * 1e6, 1),
+                "min_us": round(t[0] * 1e6, 1),
+                "max_us": round(t[-1] * 1e6, 1),
+                "gb_per_s": round(nbytes[k] / med / 1e9, 1),
+            }
+            print(f"{name} {k:9s} median {med*1e6:9.1f} us  "
+                  f"[{t[0]*1e6:.1f} .. {t[-1]*1e6:.1f}]  "
+                  f"{nbytes[k]/med/1e9:7.0f} GB/s (read+written)")
+        entry["sequence_over_fused"] = round(
+            statistics.median(ts["sequence"]) / statistics.median(ts["fused"]), 3)
+        print(f"{name} sequence/fused: {entry['sequence_over_fused']}")
+        # same values: bf16 may differ where the sequence rounded the
+        # decoded operand to bf16 first — report, and bound by the wire's
+        # own bf16 rounding step
+        d = (out_f.float() - out_s.float()).abs()
+        entry["max_abs_diff"] = d.max().item()
+        entry["differing_fraction"] = d.ne(0).float().mean().item()
+        rel = (d / out_s.float().abs().clamp_min(1e-30)).max().item()
+        entry["max_rel_diff"] = rel
+        print(f"{name} fused vs sequence: max rel diff {rel:.3e}, "
+              f"{entry['differing_fraction']:.3e} of elements differ")
+        assert rel <= (2.0 ** -7 if es == 2 else 2.0 ** -22), rel
+        result[name] = entry
+        del a, out_f, out_s, tmp
+    print(json.dumps(result))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["codec", "axpby"], default="codec")
+    ap.add_argument("--melems", type=int, default=64,
+                    help="axpby mode: Mi elements per buffer")
     ap.add_argument("--mib", type=int, default=1024, help="bf16 buffer size")
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
@@ -35,6 +128,9 @@ def main() -> None:
 
     assert torch.cuda.is_available(), "the probe needs a GPU"
     ops._require_native()
+    if args.mode == "axpby":
+        axpby_mode(args)
+        return
     n = (args.mib << 20) // 2
     src = torch.empty(n, device="cuda", dtype=torch.bfloat16)
     ops.fill_pattern(src, seed=3, mask16=0x3FFF)  # finite positive bf16

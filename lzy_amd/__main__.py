@@ -35,7 +35,8 @@ def main() -> int:
             k: getattr(cfg, k)
             for k in (
                 "storage", "channel_transport", "channel_chunk_mb",
-                "channel_wire_cast", "exec_threads", "chain_dispatch",
+                "channel_wire_cast", "stream_wire_cast", "exec_threads",
+                "chain_dispatch",
                 "op_streams", "cache_enabled", "spill_enabled",
             )
         },

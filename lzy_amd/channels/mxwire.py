@@ -12,10 +12,14 @@ uint8, crosses RCCL and gloo alike.
 bit arithmetic on the fp32 view, byte-for-byte the layout the HIP kernels
 (``lzy_amd.ops.mx8_pack``/``mx8_unpack``) produce.  They serve CPU tensors
 and are the kernels' test oracle.  ``mx8_pack``/``mx8_unpack`` dispatch.
+
+``mx8_axpby_torch`` is the reference of the fused decode-combine
+(``lzy_amd.ops.mx8_axpby``), the combine of a wire-cast merge-tree edge
+(channels/treeplan.py); ``mx8_axpby`` dispatches the same way.
 """
 from __future__ import annotations
 
-from typing import Sequence, Union
+from typing import Optional, Sequence, Union
 
 import torch
 
@@ -89,6 +93,37 @@ def mx8_unpack_torch(buf: torch.Tensor, shape: Union[int, Sequence[int]],
     return x.reshape(-1)[:n].to(dtype).reshape(shape)
 
 
+def _f32(v: float) -> float:
+    # the kernel takes alpha/beta as C floats
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def mx8_axpby_torch(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
+                    beta: float = 1.0,
+                    out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``alpha*a + beta*decode(wire)`` with torch ops only: the reference
+    of the fused decode-combine kernel and the CPU path of wired plans.
+
+    The wire decodes to fp32 (never to a 16-bit type), ``p = x̂*beta`` is
+    rounded to fp32 as the kernel's multiply is, ``a*alpha + p`` is
+    evaluated in float64 and rounded to fp32, then to ``out_dtype``
+    (default: ``a.dtype``).  The kernel's FMA rounds the exact sum once, so
+    the two differ by at most the float64 rounding ahead of the fp32 one.
+    """
+    if a.dtype not in _MX_DTYPES:
+        raise ValueError(f"mx8_axpby: dtype must be f32/bf16/f16, got {a.dtype}")
+    out_dtype = a.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _MX_DTYPES:
+        raise ValueError(
+            f"mx8_axpby: out dtype must be f32/bf16/f16, got {out_dtype}"
+        )
+    x = mx8_unpack_torch(wire, a.numel(), torch.float32)  # checks the buffer
+    p = x * torch.tensor(_f32(beta), dtype=torch.float32, device=x.device)
+    af = a.detach().reshape(-1).to(torch.float64)
+    r = (af * _f32(alpha) + p.to(torch.float64)).to(torch.float32)
+    return r.to(out_dtype).reshape(a.shape)
+
+
 def _native(t: torch.Tensor) -> bool:
     # same rule as transport.wire_pack: a device tensor on a box with the
     # HIP library takes the kernel (ops raises NativeExtensionMissing if
@@ -115,3 +150,23 @@ def mx8_unpack(buf: torch.Tensor, shape: Union[int, Sequence[int]],
 
         return ops.mx8_unpack(buf, shape, dtype)
     return mx8_unpack_torch(buf, shape, dtype)
+
+
+def mx8_axpby(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
+              beta: float = 1.0,
+              dst: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``dst = alpha*a + beta*decode(wire)``; returns ``dst`` (a new tensor
+    like ``a`` when not given; ``dst`` may be ``a``)."""
+    if _native(a):
+        from lzy_amd import ops
+
+        return ops.mx8_axpby(a, wire, alpha, beta, dst=dst)
+    if dst is None:
+        return mx8_axpby_torch(a, wire, alpha, beta)
+    if dst.shape != a.shape:
+        raise ValueError(
+            f"mx8_axpby: dst has shape {tuple(dst.shape)}, "
+            f"expected {tuple(a.shape)}"
+        )
+    dst.copy_(mx8_axpby_torch(a, wire, alpha, beta, out_dtype=dst.dtype))
+    return dst

@@ -29,16 +29,28 @@ def streamed_reduce_pair(
     beta: float = 0.5,
     chunk_bytes: int = 64 << 20,
     group: Optional[dist.ProcessGroup] = None,
+    wire: str = "",
 ) -> Optional[torch.Tensor]:
     """Pairwise reduce of ``t`` with ``peer``'s tensor.
 
     Receiver returns ``alpha*t + beta*peer_t`` (new tensor); sender sends
     its ``t`` in chunks and returns None.  Both sides must pass the same
-    shape/dtype/chunk_bytes.
+    shape/dtype/chunk_bytes and the same ``wire``.
+
+    ``wire="mxfp8"`` (f32/bf16/f16 only): chunks are a multiple of 256
+    elements and cross the link as self-contained MXFP8 buffers
+    (docs/mxwire.md); the sender packs each one, the receiver combines
+    with the fused decode ``mx8_axpby``.
     """
+    if wire not in ("", "mxfp8"):
+        raise ValueError(f"streamed_reduce_pair: unknown wire {wire!r}")
     flat = t.detach().contiguous().view(-1)
     n = flat.numel()
     per = max(1, chunk_bytes // max(1, flat.element_size()))
+    if wire:
+        return _streamed_reduce_pair_mx(
+            t, flat, peer, is_receiver, alpha, beta, per, group
+        )
     starts = list(range(0, n, per))
 
     if not is_receiver:
@@ -82,5 +94,48 @@ def streamed_reduce_pair(
             _ops.axpby(src_c, bufs[i % 2][:ln], alpha, beta, dst=dst_c)
         else:
             torch.add(src_c * alpha, bufs[i % 2][:ln], alpha=beta, out=dst_c)
+        inflight = nxt
+    return out.view(t.shape)
+
+
+def _streamed_reduce_pair_mx(t, flat, peer, is_receiver, alpha, beta, per, group):
+    from lzy_amd.channels import mxwire
+
+    if flat.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(
+            f"streamed_reduce_pair: wire=mxfp8 needs f32/bf16/f16, "
+            f"got {flat.dtype}"
+        )
+    n = flat.numel()
+    per = -(-per // 256) * 256  # whole blocks, 16 B-aligned chunk starts
+    starts = list(range(0, n, per))
+
+    if not is_receiver:
+        # packed chunks stay alive until their sends are waited on
+        packed = [mxwire.mx8_pack(flat[s: min(s + per, n)]) for s in starts]
+        works = [dist.isend(p, dst=peer, group=group) for p in packed]
+        for w in works:
+            w.wait()
+        return None
+
+    out = torch.empty_like(flat)
+    bufs = [
+        torch.empty(mxwire.mx8_nbytes(min(per, n)), dtype=torch.uint8,
+                    device=flat.device)
+        for _ in range(2)
+    ]
+
+    def post(i: int):
+        s = starts[i]
+        ln = min(s + per, n) - s
+        wb = bufs[i % 2][: mxwire.mx8_nbytes(ln)]
+        return dist.irecv(wb, src=peer, group=group), s, ln, wb
+
+    inflight = post(0) if starts else None
+    for i in range(len(starts)):
+        w, s, ln, wb = inflight
+        nxt = post(i + 1) if i + 1 < len(starts) else None
+        w.wait()
+        mxwire.mx8_axpby(flat[s: s + ln], wb, alpha, beta, dst=out[s: s + ln])
         inflight = nxt
     return out.view(t.shape)

@@ -28,6 +28,13 @@ interleaving with the serve-loop-issued transfer traffic on pg_data;
 the driver keeps at most one plan active pool-wide, and per (src, dst)
 pair every rank issues chunk-major in global topo order — pairwise
 consistent by construction (checked at build time).
+
+Wire format: with ``build_plan(..., wire="mxfp8")`` (driver config
+``stream_wire_cast``) the remote edges of an f32/bf16/f16 plan cross the
+link as block-scaled FP8 chunks — each chunk a self-contained MXFP8
+buffer, packed by the sender and combined by the fused decode
+``mxwire.mx8_axpby`` on arrival (docs/mxwire.md, "Plans").  The decision
+travels in the plan; ranks never consult their own configuration.
 """
 from __future__ import annotations
 
@@ -42,6 +49,11 @@ import torch.distributed as dist
 from lzy_amd.utils.metrics import METRICS
 
 _LOG = logging.getLogger("lzy_amd.treeplan")
+
+WIRE_MODES = ("", "mxfp8")
+_WIRE_DTYPES = ("float32", "bfloat16", "float16")
+WIRE_MIN_NUMEL = 65536      # the transport's wire-cast threshold
+WIRE_CHUNK_QUANTUM = 256    # elements; chunk_elems of a wired plan
 
 
 # ---------------------------------------------------------------------------
@@ -132,6 +144,7 @@ def build_plan(
     meta_of,
     chunk_bytes: int,
     cuda_p2p: bool,
+    wire: str = "",
 ) -> Optional[dict]:
     """Construct the per-rank step schedule for one component.
 
@@ -140,7 +153,15 @@ def build_plan(
     safely folded (shape/dtype mismatch, missing owner, or per-pair
     order inconsistency) — the caller then falls back to op-by-op
     execution.
+
+    ``wire="mxfp8"`` asks for the block-scaled FP8 wire (docs/mxwire.md) on
+    the plan's remote edges.  The driver alone decides: the plan carries
+    the outcome in ``plan["wire"]`` and ranks follow it, never their own
+    configuration.  Plans of another dtype or under the transport's size
+    threshold stay exact (``"wire": ""``).
     """
+    if wire not in WIRE_MODES:
+        raise ValueError(f"build_plan: wire must be one of {WIRE_MODES}, got {wire!r}")
     out_entry_of: Dict[str, str] = {
         tid: calls[tid].entry_ids[0] for tid in member_order
     }
@@ -262,6 +283,14 @@ def build_plan(
     # into at least 4 (but never below 1 MiB of elements)
     if numel // per < 4:
         per = max((1 << 20) // elem, math.ceil(numel / 4))
+    wired = (
+        wire == "mxfp8" and dtype in _WIRE_DTYPES and numel >= WIRE_MIN_NUMEL
+    )
+    if wired:
+        # whole blocks per chunk: every chunk but the last is a multiple of
+        # 32 elements, its wire bytes start at a multiple of 264 B (8 B-
+        # aligned) and its elements 16 B-aligned — the kernels' fast path
+        per = -(-per // WIRE_CHUNK_QUANTUM) * WIRE_CHUNK_QUANTUM
     return {
         "plan_id": plan_id,
         # per-plan tag base: edge tag = (nonce + topo) so a FAILED
@@ -272,6 +301,7 @@ def build_plan(
         "dtype": dtype,
         "numel": numel,
         "chunk_elems": per,
+        "wire": "mxfp8" if wired else "",
         "device_cuda": device_cuda,
         "cuda_p2p": bool(cuda_p2p),
         "steps_by_rank": steps_by_rank,
@@ -312,6 +342,13 @@ def run_stream_plan(
     want_cuda = plan["device_cuda"] and device is not None
     on_device = want_cuda and cuda_p2p
     host_stage = want_cuda and not cuda_p2p  # oversubscribed harnesses
+    # wired plan (docs/mxwire.md, "Plans"): every chunk crosses the link as
+    # a self-contained MXFP8 buffer.  A plan dict without the key is unwired.
+    wired = plan.get("wire", "") == "mxfp8"
+    if wired:
+        from lzy_amd.channels import mxwire
+
+        wper = mxwire.mx8_nbytes(per)  # chunk j starts at byte j * wper
 
     def flat_entry(eid: str) -> torch.Tensor:
         if not store.has(eid) and not store.wait_present(eid, timeout=wait_timeout):
@@ -330,7 +367,7 @@ def run_stream_plan(
 
     recv_timeout = _dt.timedelta(seconds=wait_timeout)
 
-    stats = {"recv_wait_s": 0.0, "sends": 0, "recvs": 0}
+    stats = {"recv_wait_s": 0.0, "sends": 0, "recvs": 0, "wire_bytes": 0}
 
     def wait_recv(w) -> None:
         # gloo honors the timeout (raises instead of hanging on a dead
@@ -375,10 +412,16 @@ def run_stream_plan(
             if st["op"] == "node" and st["remote_src"] is not None:
                 seq_by_src.setdefault(st["remote_src"], []).append(st)
         recv_buf: Dict[int, torch.Tensor] = {}  # step topo -> full buffer
+        if wired:
+            recv_len = (nchunks - 1) * wper + mxwire.mx8_nbytes(
+                numel - (nchunks - 1) * per
+            )
         for src, sts in seq_by_src.items():
             for st in sts:
                 recv_buf[st["topo"]] = torch.empty(
-                    numel, dtype=dtype, device=device if on_device else None
+                    recv_len if wired else numel,
+                    dtype=torch.uint8 if wired else dtype,
+                    device=device if on_device else None,
                 )
         posted: Dict[int, int] = {s: 0 for s in seq_by_src}
         recv_works: Dict[Tuple[int, int], Any] = {}  # (topo, j) -> work
@@ -387,6 +430,13 @@ def run_stream_plan(
         def chunk_bounds(j: int) -> Tuple[int, int]:
             s = j * per
             return s, min(s + per, numel)
+
+        def recv_bounds(j: int) -> Tuple[int, int]:
+            # chunk j inside a step's receive buffer
+            s, e = chunk_bounds(j)
+            if not wired:
+                return s, e
+            return j * wper, j * wper + mxwire.mx8_nbytes(e - s)
 
         nonce = plan.get("nonce", 0)
 
@@ -405,7 +455,7 @@ def run_stream_plan(
                 k = posted[src]
                 j, st = divmod(k, width)
                 st = sts[st]
-                s, e = chunk_bounds(j)
+                s, e = recv_bounds(j)
                 recv_works[(st["topo"], j)] = dist.irecv(
                     recv_buf[st["topo"]][s:e], src=src, group=pg,
                     tag=edge_tag(st["topo"]),
@@ -413,11 +463,17 @@ def run_stream_plan(
                 posted[src] += 1
 
         send_works: List[Any] = []
-        staged: List[torch.Tensor] = []  # host staging keepalive
+        staged: List[torch.Tensor] = []  # packed / host-staged keepalive
 
         def issue_send(t: torch.Tensor, dst: int, topo: int) -> None:
             stats["sends"] += 1
             tg = edge_tag(topo)
+            if wired:
+                # pack where the chunk lives (the kernel, for a device
+                # chunk), THEN stage: only packed bytes cross PCIe
+                t = mxwire.mx8_pack(t)
+                staged.append(t)
+            stats["wire_bytes"] += t.numel() * t.element_size()
             if host_stage and t.is_cuda:
                 c = t.to("cpu")
                 staged.append(c)
@@ -465,10 +521,17 @@ def run_stream_plan(
                     post_up_to(src, flat_idx)
                     w = recv_works.pop((st["topo"], j))
                     wait_recv(w)
-                    b_c = recv_buf[st["topo"]][s:e]
+                    rs, re_ = recv_bounds(j)
+                    b_c = recv_buf[st["topo"]][rs:re_]
                     if host_stage:
                         b_c = b_c.to(a.device)
-                    combine(out[s:e], a[s:e], b_c, st["alpha"], st["beta"])
+                    if wired:
+                        # decode fused into the combine: no plan-dtype
+                        # temporary of the received chunk
+                        mxwire.mx8_axpby(a[s:e], b_c, st["alpha"], st["beta"],
+                                         dst=out[s:e])
+                    else:
+                        combine(out[s:e], a[s:e], b_c, st["alpha"], st["beta"])
                 else:
                     b = (
                         local2_flat[st["topo"]]
@@ -498,4 +561,6 @@ def run_stream_plan(
         # config block (overlap evidence)
         if results:
             results[0]["plan_stats"] = dict(stats)
+        else:  # a rank that only sent leaves
+            results.append({"plan_stats": dict(stats)})
     return results

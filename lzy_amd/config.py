@@ -48,6 +48,7 @@ class Config:
     channel_wire_cast: str = ""        # ""|fp16|bf16|mxfp8|fp8e4m3|fp8e5m2: lossy wire format (8-bit: prefer mxfp8, block-scaled, every path; plain fp8 is unscaled, RCCL-only)
     stream_merge: bool = True          # fold pair_reduce trees into streamed plans
     stream_chunk_mb: int = 32          # chunk size for streamed tree plans (1 GiB shard -> 32 chunks; pipeline fill ~2 chunks per extra level)
+    stream_wire_cast: str = ""         # ""|mxfp8: wire format of streamed tree plans (channel_wire_cast leaves plans exact); the driver decides per plan
     # HIP data-plane kernels
     hip_max_blocks: int = 0            # 0 -> kernel default grid cap
     op_streams: int = 4                # HIP streams per device for op overlap

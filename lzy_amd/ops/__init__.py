@@ -22,6 +22,7 @@ _LIB_PATH = os.path.join(os.path.dirname(__file__), "libhipops.so")
 _lib: Optional[ctypes.CDLL] = None
 _load_error: Optional[str] = None
 _MX8 = False  # libhipops.so exports lz_mx8_pack / lz_mx8_unpack
+_MX8_AXPBY = False  # ... and lz_mx8_axpby (the fused decode-combine)
 
 
 def _try_load() -> Optional[ctypes.CDLL]:
@@ -119,6 +120,17 @@ def _try_load() -> Optional[ctypes.CDLL]:
         _MX8 = True
     except AttributeError:
         _MX8 = False
+    global _MX8_AXPBY
+    try:
+        lib.lz_mx8_axpby.restype = ctypes.c_int
+        lib.lz_mx8_axpby.argtypes = [
+            ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
+            ctypes.c_void_p,
+        ]
+        _MX8_AXPBY = True
+    except AttributeError:
+        _MX8_AXPBY = False
     lib.lz_error_name.restype = ctypes.c_char_p
     lib.lz_error_name.argtypes = [ctypes.c_int]
     lib.lz_set_max_blocks.restype = None
@@ -315,6 +327,56 @@ def mx8_unpack(buf, numel_or_shape, dtype, out=None):
         )
     )
     return out
+
+
+def mx8_axpby(a, wire, alpha: float = 1.0, beta: float = 1.0, dst=None):
+    """dst = alpha*a + beta*decode(wire): the combine of a wire-cast
+    merge-tree edge with the MXFP8 decode fused in (docs/mxwire.md).
+
+    ``a`` is a device f32/bf16/f16 tensor, ``wire`` the contiguous device
+    ``uint8[mx8_nbytes(a.numel())]`` buffer of as many elements.  The
+    decoded operand enters the fp32 FMA unrounded (it is never cast to a
+    16-bit type first).  ``dst`` defaults to a new tensor like ``a``; it
+    may be ``a`` itself (in place) and may have another of the three
+    dtypes.  Returns ``dst``."""
+    import torch
+
+    if not (a.is_cuda and wire.is_cuda):
+        raise ValueError("mx8_axpby requires device tensors")
+    _mx8_check_dtype(a.dtype, "mx8_axpby")
+    n = a.numel()
+    if wire.dtype != torch.uint8 or not wire.is_contiguous() \
+            or wire.numel() != mx8_nbytes(n):
+        raise ValueError(
+            f"mx8_axpby: wire must be contiguous uint8[{mx8_nbytes(n)}] "
+            f"for {n} elements, got {wire.dtype}[{wire.numel()}]"
+        )
+    if dst is not None:
+        _check_dst("mx8_axpby", dst, n)
+        _mx8_check_dtype(dst.dtype, "mx8_axpby dst")
+    lib = _require_native()
+    if not _MX8_AXPBY:
+        raise NativeExtensionMissing(
+            f"{_LIB_PATH} is stale: it lacks lz_mx8_axpby; "
+            f"rebuild with `python setup.py build_ext --inplace --force`"
+        )
+    x = a.detach().contiguous()
+    if dst is None:
+        dst = torch.empty_like(x)
+    _check(
+        lib.lz_mx8_axpby(
+            ctypes.c_void_p(x.data_ptr()),
+            _dtype_code(x.dtype),
+            ctypes.c_void_p(wire.data_ptr()),
+            ctypes.c_void_p(dst.data_ptr()),
+            _dtype_code(dst.dtype),
+            n,
+            ctypes.c_float(alpha),
+            ctypes.c_float(beta),
+            ctypes.c_void_p(_current_stream_ptr()),
+        )
+    )
+    return dst
 
 
 def device_checksum(t, method: str = "auto") -> int:

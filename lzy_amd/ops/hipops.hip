@@ -1037,6 +1037,185 @@ extern "C" hipError_t lz_axpby(const void* a, const void* b, int src_dtype,
 }
 
 // ---------------------------------------------------------------------------
+// mx8_axpby: dst = cast(alpha*a + beta*decode(wire)) — the combine of a
+// wire-cast merge-tree edge with the MXFP8 decode fused in (docs/mxwire.md).
+//
+// The received chunk never exists in the plan dtype: unpack-to-temporary
+// followed by axpby moves ~9 B/element of bf16 through HBM, this kernel ~5
+// (2 + 33/32 read, 2 written).  Per element, with x = float(q) * 2^(b-127)
+// taken in fp32 (exact for every b, the subnormal multiplier of b == 0
+// included): dst = round(fmaf(float(a), alpha, x * beta)) — axpby_kernel's
+// operation order with b[i] replaced by x, x never rounded to 16 bits.
+//
+// Work item = 8 consecutive elements as in the sibling mx8 kernels; the 4
+// lanes of a block read the same scale byte; nothing crosses lanes.  Two
+// groups per grid-stride trip: on the unguarded path both payload loads and
+// both loads of `a` issue before either is consumed.  `a` and `dst` may be
+// the same pointer (a lane reads its 8 elements before it writes them, and
+// no other lane touches them), so neither is __restrict__ here.
+// ---------------------------------------------------------------------------
+
+typedef float lz_f32x2 __attribute__((ext_vector_type(2)));
+
+// 8 payload bytes (lo: elements 0-3, hi: 4-7) -> fp32 * mult.  v_cvt_pk_f32_fp8
+// converts two bytes per instruction; its half selector is an immediate.
+__device__ __forceinline__ void lz_mx8_decode8(uint32_t lo, uint32_t hi, float mult,
+                                               float (&x)[8]) {
+    lz_f32x2 p;
+    p = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false);
+    x[0] = p.x * mult; x[1] = p.y * mult;
+    p = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
+    x[2] = p.x * mult; x[3] = p.y * mult;
+    p = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false);
+    x[4] = p.x * mult; x[5] = p.y * mult;
+    p = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
+    x[6] = p.x * mult; x[7] = p.y * mult;
+}
+
+__device__ __forceinline__ float lz_mx8_mult(uint32_t b) {
+    return __uint_as_float(b ? (b << 23) : 0x00400000u);
+}
+
+// combine and store one group.  FULL: all 8 elements lie inside [0, n) and
+// dst + e0 is 16 B-aligned (one or two 16 B stores); otherwise guarded.
+template <typename DstT, bool FULL>
+__device__ __forceinline__ void lz_mx8_axpby_store(const float (&fa)[8], uint32_t lo,
+                                                   uint32_t hi, uint32_t b, DstT* dst,
+                                                   int64_t e0, int64_t n, float alpha,
+                                                   float beta) {
+    constexpr int V = 8;
+    float x[V];
+    lz_mx8_decode8(lo, hi, lz_mx8_mult(b), x);
+    DstT y[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k)
+        y[k] = lz_from_float<DstT>(fmaf(fa[k], alpha, x[k] * beta));
+    if (FULL) {
+        LzVec16 q[sizeof(DstT) * V / 16];
+        __builtin_memcpy(q, y, sizeof(y));
+        LzVec16* p = reinterpret_cast<LzVec16*>(dst + e0);
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(DstT) * V / 16); ++k) p[k] = q[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            if (e0 + k < n) dst[e0 + k] = y[k];
+    }
+}
+
+// one group on the guarded path (the tail, and element-aligned views)
+template <typename SrcT, typename DstT, bool ALIGNED>
+__device__ __forceinline__ void lz_mx8_axpby_one(const SrcT* a, const uint8_t* __restrict__ wire,
+                                                 const uint8_t* __restrict__ scales,
+                                                 DstT* dst, int64_t g, int64_t n,
+                                                 float alpha, float beta) {
+    const int64_t e0 = g * 8;
+    if (e0 >= n) return;  // padded tail of the last block
+    uint32_t lo = 0, hi = 0;
+    if (ALIGNED) {
+        // payload bytes of the padded tail exist: [0, 32*nblk)
+        LzVec8 pv = *reinterpret_cast<const LzVec8*>(wire + e0);
+        lo = pv.w[0];
+        hi = pv.w[1];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            lo |= (uint32_t)wire[e0 + k] << (8 * k);
+            hi |= (uint32_t)wire[e0 + 4 + k] << (8 * k);
+        }
+    }
+    const uint32_t b = scales[g >> 2];
+    float fa[8];
+    if (ALIGNED && e0 + 8 <= n) {
+        lz_mx8_load<SrcT, true>(a, e0, n, fa);
+        lz_mx8_axpby_store<DstT, true>(fa, lo, hi, b, dst, e0, n, alpha, beta);
+    } else {
+        lz_mx8_load<SrcT, false>(a, e0, n, fa);
+        lz_mx8_axpby_store<DstT, false>(fa, lo, hi, b, dst, e0, n, alpha, beta);
+    }
+}
+
+template <typename SrcT, typename DstT, bool ALIGNED>
+__global__ void __launch_bounds__(LZ_BLOCK)
+mx8_axpby_kernel(const SrcT* a, const uint8_t* __restrict__ wire, DstT* dst, int64_t n,
+                 float alpha, float beta) {
+    const int64_t nblk = (n + 31) >> 5;
+    const int64_t ngroups = nblk * 4;
+    const uint8_t* __restrict__ scales = wire + nblk * 32;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+
+    for (int64_t ga = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ga < ngroups;
+         ga += 2 * stride) {
+        const int64_t gb = ga + stride;
+        if (ALIGNED && (gb + 1) * 8 <= n) {  // ga < gb: both groups whole
+            const LzVec8 pa = *reinterpret_cast<const LzVec8*>(wire + ga * 8);
+            const LzVec8 pb = *reinterpret_cast<const LzVec8*>(wire + gb * 8);
+            const uint32_t ba = scales[ga >> 2], bb = scales[gb >> 2];
+            float fa[8], fb[8];
+            lz_mx8_load<SrcT, true>(a, ga * 8, n, fa);
+            lz_mx8_load<SrcT, true>(a, gb * 8, n, fb);
+            lz_mx8_axpby_store<DstT, true>(fa, pa.w[0], pa.w[1], ba, dst, ga * 8, n,
+                                           alpha, beta);
+            lz_mx8_axpby_store<DstT, true>(fb, pb.w[0], pb.w[1], bb, dst, gb * 8, n,
+                                           alpha, beta);
+        } else {
+            lz_mx8_axpby_one<SrcT, DstT, ALIGNED>(a, wire, scales, dst, ga, n, alpha, beta);
+            if (gb < ngroups)
+                lz_mx8_axpby_one<SrcT, DstT, ALIGNED>(a, wire, scales, dst, gb, n, alpha,
+                                                      beta);
+        }
+    }
+}
+
+// a: n elements of a_dtype; wire_u8: 33*ceil(n/32) bytes; dst: n elements of
+// dst_dtype (both f32/f16/bf16).  dst == a is allowed, partial overlap is not.
+extern "C" hipError_t lz_mx8_axpby(const void* a, int a_dtype, const void* wire_u8,
+                                   void* dst, int dst_dtype, int64_t n, float alpha,
+                                   float beta, void* stream) {
+    if (a_dtype != LZ_F32 && a_dtype != LZ_F16 && a_dtype != LZ_BF16)
+        return hipErrorInvalidValue;
+    if (dst_dtype != LZ_F32 && dst_dtype != LZ_F16 && dst_dtype != LZ_BF16)
+        return hipErrorInvalidValue;
+    if (n < 0) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    const int blocks = lz_mx8_grid(n);
+    const bool aligned = (((uintptr_t)a & 15) == 0) && (((uintptr_t)dst & 15) == 0) &&
+                         (((uintptr_t)wire_u8 & 7) == 0);
+#define LZ_MXA_DST(SrcT, code, DstT)                                            \
+    case code:                                                                  \
+        if (aligned)                                                            \
+            hipLaunchKernelGGL((mx8_axpby_kernel<SrcT, DstT, true>),            \
+                               dim3(blocks), dim3(LZ_BLOCK), 0, s,              \
+                               (const SrcT*)a, (const uint8_t*)wire_u8,         \
+                               (DstT*)dst, n, alpha, beta);                     \
+        else                                                                    \
+            hipLaunchKernelGGL((mx8_axpby_kernel<SrcT, DstT, false>),           \
+                               dim3(blocks), dim3(LZ_BLOCK), 0, s,              \
+                               (const SrcT*)a, (const uint8_t*)wire_u8,         \
+                               (DstT*)dst, n, alpha, beta);                     \
+        break;
+#define LZ_MXA_SRC(scode, SrcT)                                                 \
+    case scode:                                                                 \
+        switch (dst_dtype) {                                                    \
+            LZ_MXA_DST(SrcT, LZ_F32, float)                                     \
+            LZ_MXA_DST(SrcT, LZ_F16, __half)                                    \
+            LZ_MXA_DST(SrcT, LZ_BF16, __hip_bfloat16)                           \
+            default: return hipErrorInvalidValue;                               \
+        }                                                                       \
+        break;
+    switch (a_dtype) {
+        LZ_MXA_SRC(LZ_F32, float)
+        LZ_MXA_SRC(LZ_F16, __half)
+        LZ_MXA_SRC(LZ_BF16, __hip_bfloat16)
+        default: return hipErrorInvalidValue;
+    }
+#undef LZ_MXA_SRC
+#undef LZ_MXA_DST
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // transpose_cast: dst[c][r] = cast(src[r][c]) — LDS-staged 64x64 tiles.
 //
 // The pack kernel for non-contiguous (transposed) tensors: a naive

@@ -1174,6 +1174,14 @@ class _DriverScheduler:
         self.active_plan: Optional[dict] = None
         self.deferred_plans: List[int] = []
         self._stream_chunk = int(getattr(cfg, "stream_chunk_mb", 64)) << 20
+        # wire format of streamed plans; the driver decides, the plan
+        # carries it to the ranks (channel_wire_cast leaves plans exact)
+        self._stream_wire = str(getattr(cfg, "stream_wire_cast", "") or "")
+        if self._stream_wire not in ("", "mxfp8"):
+            raise ValueError(
+                f"stream_wire_cast must be \"\" or \"mxfp8\", "
+                f"got {self._stream_wire!r}"
+            )
         # explicit ipc mode, or automatic when ranks outnumber GPUs:
         # RCCL cannot build a comm then, and the host-staged fallback is
         # ~19x slower than hipIpc zero-copy for device tensors on one
@@ -1863,6 +1871,7 @@ class _DriverScheduler:
             comp["order"], self.calls, meta_of,
             chunk_bytes=self._stream_chunk,
             cuda_p2p=bool(agent_tr is not None and agent_tr._cuda_p2p),
+            wire=self._stream_wire,
         )
         if plan is None:
             _LOG.info("stream component %d not foldable — op-by-op", cid)
@@ -1899,10 +1908,21 @@ class _DriverScheduler:
             len(st.get("send_to", ())) for sts in steps_by_rank.values()
             for st in sts
         )
-        elem = torch.empty(0, dtype=getattr(torch, plan["dtype"])).element_size()
+        if plan["wire"]:
+            # a wired edge carries one MXFP8 buffer per chunk
+            from lzy_amd.channels.mxwire import mx8_nbytes
+
+            per, numel = plan["chunk_elems"], plan["numel"]
+            edge_bytes = sum(
+                mx8_nbytes(min(per, numel - s)) for s in range(0, numel, per)
+            )
+        else:
+            elem = torch.empty(
+                0, dtype=getattr(torch, plan["dtype"])).element_size()
+            edge_bytes = plan["numel"] * elem
         METRICS.inc("lzy_stream_plans")
         METRICS.inc("lzy_transfers", n_edges)
-        METRICS.inc("lzy_transfer_bytes", n_edges * plan["numel"] * elem)
+        METRICS.inc("lzy_transfer_bytes", n_edges * edge_bytes)
         _LOG.info(
             "stream plan %s: %d nodes on ranks %s, %d cross edges",
             plan["plan_id"], len(comp["order"]), plan["participants"], n_edges,
@@ -1935,7 +1955,11 @@ class _DriverScheduler:
                     METRICS.observe(
                         "lzy_plan_recv_wait_s", float(ps.get("recv_wait_s", 0.0))
                     )
-            by_task = {w["task"]: w for w in ap["outputs"]}
+                    METRICS.inc(
+                        "lzy_stream_wire_bytes", int(ps.get("wire_bytes", 0))
+                    )
+            # (a rank that only sent leaves reports a bare stats record)
+            by_task = {w["task"]: w for w in ap["outputs"] if "task" in w}
             for m in comp["order"]:
                 wire = by_task.get(m)
                 if wire is not None:
