@@ -9,6 +9,9 @@ on one MI355X node a channel edge is
   * device tensor, cross -> RCCL point-to-point over xGMI
                             (torch.distributed isend/irecv on the data
                             process group; "nccl" IS RCCL on ROCm);
+  * container of tensors -> one packed uint8 buffer over the same tensor
+                            path, leaves rebuilt as views of it
+                            (channels/bundle.py, docs/bundles.md);
   * anything else        -> cloudpickle bytes over gloo isend/irecv.
 
 Ordering discipline: RCCL matches p2p by (src, dst) issue order, not tags,
@@ -33,6 +36,7 @@ _LOG = logging.getLogger("lzy_amd.transport")
 
 KIND_TENSOR = "tensor"
 KIND_BYTES = "bytes"
+KIND_BUNDLE = "bundle"  # container of tensors, packed (channels/bundle.py)
 
 
 @dataclass
@@ -47,9 +51,10 @@ class EntryMeta:
     device_type: str = "cpu"  # "cuda" -> lives in HBM on the owner
     nbytes: int = 0
     ipc_handle: Optional[bytes] = None  # driver-side cache; never on the wire
+    bundle: Optional[dict] = None  # KIND_BUNDLE only: bundle.bundle_spec()
 
     def to_wire(self) -> dict:
-        return {
+        wire = {
             "entry_id": self.entry_id,
             "kind": self.kind,
             "shape": list(self.shape),
@@ -57,6 +62,9 @@ class EntryMeta:
             "device_type": self.device_type,
             "nbytes": self.nbytes,
         }
+        if self.kind == KIND_BUNDLE:
+            wire["bundle"] = self.bundle
+        return wire
 
     @staticmethod
     def from_wire(d: dict) -> "EntryMeta":
@@ -67,7 +75,34 @@ class EntryMeta:
             dtype=d["dtype"],
             device_type=d["device_type"],
             nbytes=d["nbytes"],
+            bundle=d.get("bundle"),
         )
+
+
+def bundles_enabled() -> bool:
+    from lzy_amd.config import get_config
+
+    return get_config().channel_bundles
+
+
+def _bundle_meta(entry_id: str, value: Any) -> Optional[EntryMeta]:
+    """Bundle meta of an eligible container (no pickling, no device
+    work); None for everything else or with ``channel_bundles`` off."""
+    from lzy_amd.channels import bundle as _bundle
+
+    if type(value) not in _bundle._CONTAINERS or not bundles_enabled():
+        return None
+    got = _bundle._analyze(value)
+    if got is None:
+        return None
+    spec = _bundle._spec_of(*got)
+    return EntryMeta(
+        entry_id=entry_id,
+        kind=KIND_BUNDLE,
+        device_type=got[1][0].device.type,
+        nbytes=spec["nbytes"],
+        bundle=spec,
+    )
 
 
 def describe_value(entry_id: str, value: Any) -> EntryMeta:
@@ -80,6 +115,9 @@ def describe_value(entry_id: str, value: Any) -> EntryMeta:
             device_type=value.device.type,
             nbytes=value.numel() * value.element_size(),
         )
+    bm = _bundle_meta(entry_id, value)
+    if bm is not None:
+        return bm
     data = pickle_value(value)
     return EntryMeta(entry_id=entry_id, kind=KIND_BYTES, nbytes=len(data))
 
@@ -301,8 +339,15 @@ class Transport:
     # their xGMI links instead of serializing on the comm stream.
 
     def send_ops(self, value: Any, prepickled: Optional[bytes], dst: int,
-                 offset_chunks: int = 0, tag: int = 0):
+                 offset_chunks: int = 0, tag: int = 0,
+                 kind: Optional[str] = None):
         """Build send P2POps; returns (ops, keepalive).
+
+        ``kind``: the entry's ``EntryMeta.kind`` when the caller knows it —
+        the receiver follows the meta, so a sender told the kind never
+        re-derives it.  Without it a container is sent as a bundle exactly
+        when ``describe_value`` would have said so (no stored pickle, an
+        eligible value, ``channel_bundles`` on).
 
         ``offset_chunks`` resumes a partially completed transfer: the
         first ``offset_chunks`` chunks are assumed delivered and skipped.
@@ -312,6 +357,20 @@ class Transport:
         NCCL/RCCL ignores tags — that path keeps the strict
         driver-sequenced issue-order discipline instead.
         """
+        as_bundle = kind == KIND_BUNDLE or (
+            kind is None
+            and prepickled is None
+            and not isinstance(value, torch.Tensor)
+            and _bundle_meta("", value) is not None
+        )
+        if as_bundle:
+            from lzy_amd.channels import bundle as _bundle
+
+            # one segmented-copy launch (torch codec for CPU leaves); the
+            # packed uint8 buffer then rides the tensor path below, exact:
+            # channel_wire_cast never applies to bundles (uint8 is not a
+            # castable dtype, and the receiver never casts this kind)
+            value = _bundle.pack_bundle(value)
         if isinstance(value, torch.Tensor):
             t = value.detach()
             if not t.is_contiguous():
@@ -362,6 +421,36 @@ class Transport:
 
         ``offset_chunks``/``into`` resume into an existing buffer that
         already holds the first ``offset_chunks`` chunks."""
+        if meta.kind == KIND_BUNDLE:
+            # the sender's packed uint8 buffer over the tensor path (same
+            # chunking, staging and tag rules, never cast); the leaves are
+            # views of this one buffer on OUR device.  Follows meta.kind
+            # alone — the local channel_bundles setting is not consulted.
+            from lzy_amd.channels import bundle as _bundle
+
+            spec = meta.bundle
+            want_cuda = meta.device_type == "cuda" and self._device is not None
+            on_device = want_cuda and self._cuda_p2p
+            buf = into if into is not None else torch.empty(
+                spec["nbytes"], dtype=torch.uint8,
+                device=self._device if on_device else None,
+            )
+            per = self._chunk_elems(1)
+            if buf.numel() <= per and offset_chunks == 0:
+                chunks = [buf]
+            else:
+                chunks = self._chunks(buf, per, offset_chunks)
+            eff = 0 if buf.is_cuda else tag  # mirror of the sender rule
+            ops = [dist.P2POp(dist.irecv, c, src, group=self._pg, tag=eff)
+                   for c in chunks]
+
+            def finalize_bundle():
+                out = buf
+                if want_cuda and not on_device:
+                    out = out.to(self._device, non_blocking=False)
+                return _bundle.unpack_bundle(out, spec)
+
+            return ops, finalize_bundle
         if meta.kind == KIND_TENSOR:
             dtype = getattr(torch, meta.dtype)
             wire_dtype = dtype
@@ -476,9 +565,11 @@ class Transport:
     # -- single-transfer conveniences ----------------------------------------
 
     def isend_value(self, value: Any, prepickled: Optional[bytes], dst: int,
-                    offset_chunks: int = 0, tag: int = 0):
+                    offset_chunks: int = 0, tag: int = 0,
+                    kind: Optional[str] = None):
         """Issue non-blocking send(s); returns (works, keepalive)."""
-        ops, keep = self.send_ops(value, prepickled, dst, offset_chunks, tag)
+        ops, keep = self.send_ops(value, prepickled, dst, offset_chunks, tag,
+                                  kind)
         return self.issue(ops), keep
 
     def irecv_value(self, meta: EntryMeta, src: int, offset_chunks: int = 0,

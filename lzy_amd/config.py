@@ -46,7 +46,8 @@ class Config:
     channel_transport: str = "rccl"    # "rccl" | "ipc"
     channel_chunk_mb: int = 256        # chunk size for large-tensor transfers
     channel_wire_cast: str = ""        # ""|fp16|bf16|mxfp8|fp8e4m3|fp8e5m2: lossy wire format (8-bit: prefer mxfp8, block-scaled, every path; plain fp8 is unscaled, RCCL-only)
-    stream_merge: bool = True          # fold pair_reduce trees into streamed plans
+    channel_bundles: bool = True       # dict/list/tuple nests of tensors travel as packed bundles, not pickles (docs/bundles.md)
+    stream_merge: bool = True         # fold pair_reduce trees into streamed plans
     stream_chunk_mb: int = 32          # chunk size for streamed tree plans (1 GiB shard -> 32 chunks; pipeline fill ~2 chunks per extra level)
     stream_wire_cast: str = ""         # ""|mxfp8: wire format of streamed tree plans (channel_wire_cast leaves plans exact); the driver decides per plan
     # HIP data-plane kernels

@@ -23,6 +23,9 @@ _lib: Optional[ctypes.CDLL] = None
 _load_error: Optional[str] = None
 _MX8 = False  # libhipops.so exports lz_mx8_pack / lz_mx8_unpack
 _MX8_AXPBY = False  # ... and lz_mx8_axpby (the fused decode-combine)
+_SEGCOPY = False  # ... and lz_segcopy (the packed-bundle gather/scatter)
+# bytes per tile of the segmented copy — LZ_SEG_TILE in hipops.hip
+SEGCOPY_TILE = 16384
 
 
 def _try_load() -> Optional[ctypes.CDLL]:
@@ -131,6 +134,20 @@ def _try_load() -> Optional[ctypes.CDLL]:
         _MX8_AXPBY = True
     except AttributeError:
         _MX8_AXPBY = False
+    global _SEGCOPY
+    try:
+        lib.lz_segcopy.restype = ctypes.c_int
+        lib.lz_segcopy.argtypes = [
+            ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+            ctypes.c_void_p,
+        ]
+        lib.lz_segcopy_tile.restype = ctypes.c_int
+        lib.lz_segcopy_tile.argtypes = []
+        # the host builds tile_start for SEGCOPY_TILE: a library compiled
+        # for another tile size is as unusable as one without the export
+        _SEGCOPY = lib.lz_segcopy_tile() == SEGCOPY_TILE
+    except AttributeError:
+        _SEGCOPY = False
     lib.lz_error_name.restype = ctypes.c_char_p
     lib.lz_error_name.argtypes = [ctypes.c_int]
     lib.lz_set_max_blocks.restype = None
@@ -377,6 +394,263 @@ def mx8_axpby(a, wire, alpha: float = 1.0, beta: float = 1.0, dst=None):
         )
     )
     return dst
+
+
+# ---------------------------------------------------------------------------
+# segmented copy: pack / unpack a list of tensors into one uint8 buffer
+# (the wire form of a tensor bundle — channels/bundle.py, docs/bundles.md)
+# ---------------------------------------------------------------------------
+
+def _require_segcopy() -> ctypes.CDLL:
+    lib = _require_native()
+    if not _SEGCOPY:
+        raise NativeExtensionMissing(
+            f"{_LIB_PATH} is stale: it lacks lz_segcopy (tile {SEGCOPY_TILE}); "
+            f"rebuild with `python setup.py build_ext --inplace --force`"
+        )
+    return lib
+
+
+def _check_align(align: int) -> int:
+    align = int(align)
+    if align < 1 or align & (align - 1):
+        raise ValueError(f"align must be a positive power of two, got {align}")
+    return align
+
+
+def segcopy_layout(sizes, align: int = 128):
+    """Byte offsets of segments of ``sizes`` bytes laid out in order, each
+    starting at a multiple of ``align``; returns ``(offsets, total)`` with
+    ``total`` the end of the last segment rounded up to ``align``.  Pure
+    host arithmetic."""
+    align = _check_align(align)
+    offsets = []
+    end = 0
+    for n in sizes:
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"negative segment size {n}")
+        off = (end + align - 1) // align * align
+        offsets.append(off)
+        end = off + n
+    return offsets, (end + align - 1) // align * align
+
+
+def segcopy_nbytes(sizes, align: int = 128) -> int:
+    """Length of the packed buffer for segments of ``sizes`` bytes."""
+    return segcopy_layout(sizes, align)[1]
+
+
+def segcopy_table(src_addrs, dst_addrs, sizes, tile: int = SEGCOPY_TILE):
+    """The kernel's table for ``len(sizes)`` segments, as a flat list of
+    ints — ``src_addr[n] + dst_addr[n] + nbytes[n] + tile_start[n + 1]`` —
+    and the tile count.  ``tile_start`` is the prefix sum of
+    ``ceil(nbytes / tile)``: a zero-length segment owns no tile.  Pure host
+    code (no device needed)."""
+    sizes = [int(n) for n in sizes]
+    if not (len(src_addrs) == len(dst_addrs) == len(sizes)):
+        raise ValueError("segcopy_table: length mismatch")
+    tile_start = [0]
+    for n in sizes:
+        if n < 0:
+            raise ValueError(f"negative segment size {n}")
+        tile_start.append(tile_start[-1] + (n + tile - 1) // tile)
+    table = [int(a) for a in src_addrs] + [int(a) for a in dst_addrs] \
+        + sizes + tile_start
+    return table, tile_start[-1]
+
+
+def _nbytes_of(t) -> int:
+    return t.numel() * t.element_size()
+
+
+def _byte_view(t):
+    """Flat uint8 view of a contiguous tensor (0-dim and empty included)."""
+    import torch
+
+    return t.reshape(-1).view(torch.uint8)
+
+
+def pack_tensors_torch(tensors, out=None, align: int = 128):
+    """Torch-only twin of :func:`pack_tensors`, byte-identical to the
+    kernel's output: the codec of CPU bundles and the kernel's test oracle
+    (the role ``mx8_pack_torch`` has for the MXFP8 kernels)."""
+    import torch
+
+    tensors = list(tensors)
+    offsets, total = segcopy_layout([_nbytes_of(t) for t in tensors], align)
+    if out is None:
+        device = tensors[0].device if tensors else None
+        out = torch.zeros(total, dtype=torch.uint8, device=device)
+    else:
+        if out.dtype != torch.uint8 or not out.is_contiguous() \
+                or out.numel() != total:
+            raise ValueError(
+                f"pack_tensors_torch: out must be a contiguous uint8[{total}]"
+            )
+        out.zero_()
+    for t, off in zip(tensors, offsets):
+        n = _nbytes_of(t)
+        if n:
+            out[off: off + n].copy_(_byte_view(t.detach().contiguous()))
+    return out, offsets
+
+
+def _segcopy_upload(table, device):
+    """The table in device memory, uploaded on ``device``'s current stream.
+    Pinned staging + async H2D: torch's pinned allocator keeps the host
+    block until the copy has run, its device allocator keeps the table
+    until the kernels launched on the same stream afterwards have."""
+    import torch
+
+    host = torch.empty(len(table), dtype=torch.int64, pin_memory=True)
+    host.copy_(torch.tensor(table, dtype=torch.int64))
+    with torch.cuda.device(device):
+        return host.to(device, non_blocking=True)
+
+
+def _segcopy_run(lib, dev_table, nseg: int, ntiles: int, zero_pad_align: int,
+                 device) -> None:
+    import torch
+
+    with torch.cuda.device(device):
+        _check(
+            lib.lz_segcopy(
+                ctypes.c_void_p(dev_table.data_ptr()),
+                nseg,
+                ntiles,
+                int(zero_pad_align),
+                ctypes.c_void_p(_current_stream_ptr()),
+            )
+        )
+
+
+def _segcopy_launch(lib, src_addrs, dst_addrs, sizes, zero_pad_align: int,
+                    device) -> None:
+    table, ntiles = segcopy_table(src_addrs, dst_addrs, sizes)
+    if ntiles == 0:
+        return
+    dev_table = _segcopy_upload(table, device)
+    _segcopy_run(lib, dev_table, len(sizes), ntiles, zero_pad_align, device)
+
+
+def pack_tensors(tensors, out=None, align: int = 128):
+    """Pack device tensors into one contiguous device ``uint8`` buffer with
+    a single segmented-copy launch on the current stream.
+
+    Leaves are laid out in order, each at a multiple of ``align`` (128 B: an
+    L2 line, and enough for any dtype's view and for 16 B vector access);
+    the buffer is ``segcopy_nbytes(sizes, align)`` long and every byte of it
+    is defined — leaf data or zero.  Non-contiguous leaves go through
+    ``.contiguous()`` first.  Returns ``(buf, offsets)``; ``out`` (device
+    ``uint8`` of exactly that length, ``align``-aligned) is filled in place
+    when given."""
+    import torch
+
+    # (a state_dict has hundreds of leaves: the host work per leaf is kept
+    # to the few attribute reads below)
+    tensors = [t.detach() if t.requires_grad else t for t in tensors]
+    align = _check_align(align)
+    if not tensors:
+        raise ValueError("pack_tensors: no tensors")
+    device = tensors[0].device
+    sizes = []
+    for t in tensors:
+        if not t.is_cuda:
+            raise ValueError("pack_tensors requires device tensors")
+        if t.device != device:
+            raise ValueError(
+                f"pack_tensors: leaves on different devices "
+                f"({device}, {t.device})"
+            )
+        sizes.append(t.numel() * t.element_size())
+    offsets, total = segcopy_layout(sizes, align)
+    if out is not None:
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.dim() == 1
+                and out.is_contiguous()):
+            raise ValueError("pack_tensors: out must be a contiguous device uint8")
+        if out.numel() != total:
+            raise ValueError(
+                f"pack_tensors: out has {out.numel()} bytes, expected {total}"
+            )
+        if out.device != device:
+            raise ValueError("pack_tensors: out is on another device")
+        if out.data_ptr() % align:
+            raise ValueError(f"pack_tensors: out must be {align} B-aligned")
+    lib = _require_segcopy()
+    if out is None:
+        # the pad is zeroed by address, so the base must be align-aligned;
+        # the allocator's own alignment covers the default
+        raw = torch.empty(total + align, dtype=torch.uint8, device=device)
+        skew = -raw.data_ptr() % align
+        out = raw[skew: skew + total]
+    srcs = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    base = out.data_ptr()
+    _segcopy_launch(
+        lib, [s.data_ptr() for s in srcs], [base + o for o in offsets],
+        sizes, align, device,
+    )
+    return out, offsets
+
+
+def _numel_of(shape) -> int:
+    n = 1
+    for d in shape:
+        n *= int(d)
+    return n
+
+
+def unpack_tensors(buf, offsets, shapes, dtypes, out=None):
+    """Leaves of a packed buffer.  With ``out=None`` they are VIEWS into
+    ``buf`` (no kernel, no copy; CPU or device).  With ``out`` a list of
+    contiguous device tensors of the leaves' shapes and dtypes the bytes
+    are scattered into them by the segmented-copy kernel (the
+    ``load_state_dict``-style "copy into my parameters" case) and ``out``
+    is returned."""
+    import torch
+
+    if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
+        raise ValueError("unpack_tensors: buf must be a contiguous 1-D uint8")
+    if not (len(offsets) == len(shapes) == len(dtypes)):
+        raise ValueError("unpack_tensors: offsets/shapes/dtypes differ in length")
+    shapes = [tuple(int(d) for d in s) for s in shapes]
+    sizes = [
+        _numel_of(s) * torch.empty(0, dtype=dt).element_size()
+        for s, dt in zip(shapes, dtypes)
+    ]
+    for off, n in zip(offsets, sizes):
+        if off < 0 or off + n > buf.numel():
+            raise ValueError(
+                f"unpack_tensors: segment [{off}, {off + n}) outside the "
+                f"{buf.numel()}-byte buffer"
+            )
+    if out is None:
+        return [
+            buf[off: off + n].view(dt).view(s)
+            for off, n, s, dt in zip(offsets, sizes, shapes, dtypes)
+        ]
+    out = list(out)
+    if not buf.is_cuda:
+        raise ValueError("unpack_tensors: scatter requires a device buffer")
+    if len(out) != len(offsets):
+        raise ValueError("unpack_tensors: out has the wrong number of tensors")
+    for o, s, dt in zip(out, shapes, dtypes):
+        if not o.is_cuda or o.device != buf.device:
+            raise ValueError("unpack_tensors: out tensors must be on buf's device")
+        if not o.is_contiguous():
+            raise ValueError("unpack_tensors: out tensors must be contiguous")
+        if o.dtype != dt or tuple(o.shape) != s:
+            raise ValueError(
+                f"unpack_tensors: out tensor is {o.dtype}{tuple(o.shape)}, "
+                f"expected {dt}{s}"
+            )
+    lib = _require_segcopy()
+    base = buf.data_ptr()
+    _segcopy_launch(
+        lib, [base + o for o in offsets], [o.data_ptr() for o in out],
+        sizes, 0, buf.device,
+    )
+    return out
 
 
 def device_checksum(t, method: str = "auto") -> int:

@@ -1358,6 +1358,157 @@ extern "C" hipError_t lz_transpose_cast(const void* src, int src_dtype,
 }
 
 // ---------------------------------------------------------------------------
+// segcopy: many (src, dst, nbytes) byte copies in ONE launch — the gather
+// that packs a container's tensor leaves into one wire buffer, and the
+// scatter that copies a received buffer into user tensors
+// (channels/bundle.py, docs/bundles.md).
+// ---------------------------------------------------------------------------
+//
+// Table (int64, device memory): src_addr[nseg], dst_addr[nseg], nbytes[nseg],
+// tile_start[nseg + 1].  Segment s owns tiles [tile_start[s], tile_start[s+1])
+// of LZ_SEG_TILE bytes each (the last one partial); zero-length segments own
+// none.  A workgroup grid-strides over tiles; the tile index is a function of
+// blockIdx alone, so the binary search over tile_start and the table reads
+// are wave-uniform (scalar loads).
+//
+// Tile size: 16 KiB = 256 lanes x 16 B x 4.  Every lane issues its 4
+// independent 16 B loads before the first store, and at the default grid cap
+// 4 workgroups share a CU, i.e. 16 loads per lane slot and 64 KiB per CU in
+// flight — above the >= 8 loads per lane / ~32 KiB per CU at which a
+// streaming read stops being latency-bound on MI355X.  Measured with the
+// table already on the device (benchmarks/bundle_probe.py, "kernel"): 1 GiB
+// moves at 5.0 TB/s read+written as one segment and as 512 mixed ones alike,
+// the rate of a plain copy of one buffer, so a larger tile has nothing left
+// to buy (32 and 64 KiB builds measured the same) and would only coarsen the
+// balance of small leaves: a state_dict is mostly biases and norms of a few
+// KiB.
+//
+// Access width: LZ_SEG_TILE is a multiple of 16, so every tile of a segment
+// has the alignment of the segment's own (src | dst).  Both 16 B-aligned ->
+// 16 B vectors; otherwise the widest power of two dividing both addresses,
+// down to single bytes.  The < width trailing bytes of a tile go bytewise.
+// Nothing before src / past src + nbytes is read; nothing outside
+// [dst, dst + nbytes) is written except, with zero_pad_align > 0, the zero
+// fill of [dst + nbytes, align_up(dst + nbytes, zero_pad_align)) by the
+// segment's last tile (the pack direction: every byte of the packed buffer
+// is then defined, so buffers compare and hash equal).
+#ifndef LZ_SEG_TILE
+#define LZ_SEG_TILE 16384
+#endif
+static_assert(LZ_SEG_TILE % (LZ_BLOCK * 16) == 0, "tile = whole 16 B sweeps");
+
+extern "C" int lz_segcopy_tile() { return LZ_SEG_TILE; }
+
+// The table holds addresses as integers.  A pointer made from one is a
+// generic ("flat") pointer unless it is given the global address space by
+// hand, and flat accesses wait for the LDS counter as well as the memory
+// one.  Clang's native vector types (unlike uint4, a class) load and store
+// through address-space-qualified pointers.
+#define LZ_GLOBAL __attribute__((address_space(1)))
+typedef uint32_t lz_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t lz_u32x2 __attribute__((ext_vector_type(2)));
+
+template <typename V>
+__device__ __forceinline__ void lz_seg_tile_copy(uint64_t sa, uint64_t da,
+                                                 int len) {
+    constexpr int U = LZ_SEG_TILE / (LZ_BLOCK * 16);  // loads in flight per lane
+    constexpr int SWEEP = U * LZ_BLOCK;
+    const int nv = len / (int)sizeof(V);
+    const LZ_GLOBAL V* sv = (const LZ_GLOBAL V*)sa;
+    LZ_GLOBAL V* dv = (LZ_GLOBAL V*)da;
+    const int tid = (int)threadIdx.x;
+    int base = 0;
+    // whole sweeps: U independent loads issued back to back, then U stores
+    for (; base + SWEEP <= nv; base += SWEEP) {
+        V r[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) r[k] = sv[base + k * LZ_BLOCK + tid];
+#pragma unroll
+        for (int k = 0; k < U; ++k) dv[base + k * LZ_BLOCK + tid] = r[k];
+    }
+    // the partial sweep: loads stay unconditional (index clamped into the
+    // tile, so nothing outside it is read) and only the stores are guarded
+    // — a branch around each load would make every one of them wait
+    if (base < nv) {
+        V r[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const int i = base + k * LZ_BLOCK + tid;
+            r[k] = sv[i < nv ? i : nv - 1];
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const int i = base + k * LZ_BLOCK + tid;
+            if (i < nv) dv[i] = r[k];
+        }
+    }
+    // trailing len % sizeof(V) bytes (< 16 <= LZ_BLOCK): one byte per lane
+    const int t = nv * (int)sizeof(V) + tid;
+    if (t < len)
+        ((LZ_GLOBAL uint8_t*)da)[t] = ((const LZ_GLOBAL uint8_t*)sa)[t];
+}
+
+__global__ void __launch_bounds__(LZ_BLOCK)
+segcopy_kernel(const int64_t* __restrict__ table, int64_t nseg, int64_t ntiles,
+               int zero_pad_align) {
+    const int64_t* __restrict__ src_addr = table;
+    const int64_t* __restrict__ dst_addr = table + nseg;
+    const int64_t* __restrict__ seg_bytes = table + 2 * nseg;
+    const int64_t* __restrict__ tile_start = table + 3 * nseg;
+
+    int64_t lo = 0;  // a block's tiles ascend, so its segment index does too
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        // largest s with tile_start[s] <= tile; invariant
+        // tile_start[lo] <= tile < tile_start[hi] (tile_start[0] == 0,
+        // tile_start[nseg] == ntiles), so empty segments are skipped.  A
+        // tile still inside the previous segment needs no search.
+        if (tile >= tile_start[lo + 1]) {
+            int64_t hi = nseg;
+            while (hi - lo > 1) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (tile_start[mid] <= tile) lo = mid; else hi = mid;
+            }
+        }
+        const int64_t nb = seg_bytes[lo];
+        const int64_t off = (tile - tile_start[lo]) * (int64_t)LZ_SEG_TILE;
+        const int64_t rest = nb - off;
+        if (rest <= 0) continue;  // malformed table: never index past a segment
+        const int len = (int)(rest < LZ_SEG_TILE ? rest : LZ_SEG_TILE);
+        const uint64_t sa = (uint64_t)src_addr[lo] + (uint64_t)off;
+        const uint64_t da = (uint64_t)dst_addr[lo] + (uint64_t)off;
+        const unsigned mis = (unsigned)((sa | da) & 15u);
+        if (mis == 0) lz_seg_tile_copy<lz_u32x4>(sa, da, len);
+        else if ((mis & 7u) == 0) lz_seg_tile_copy<lz_u32x2>(sa, da, len);
+        else if ((mis & 3u) == 0) lz_seg_tile_copy<uint32_t>(sa, da, len);
+        else if ((mis & 1u) == 0) lz_seg_tile_copy<uint16_t>(sa, da, len);
+        else lz_seg_tile_copy<uint8_t>(sa, da, len);
+
+        if (zero_pad_align > 0 && rest <= LZ_SEG_TILE) {  // segment's last tile
+            const uint64_t end = (uint64_t)dst_addr[lo] + (uint64_t)nb;
+            const uint64_t a = (uint64_t)zero_pad_align;
+            const int pad = (int)((end + a - 1) / a * a - end);
+            LZ_GLOBAL uint8_t* p = (LZ_GLOBAL uint8_t*)end;
+            for (int i = (int)threadIdx.x; i < pad; i += LZ_BLOCK) p[i] = 0;
+        }
+    }
+}
+
+// No allocation, synchronisation or copy here: the caller owns the device
+// table and has ordered its upload before this launch on ``stream``.
+extern "C" hipError_t lz_segcopy(const void* table_dev, int64_t nseg,
+                                 int64_t ntiles, int zero_pad_align,
+                                 void* stream) {
+    if (nseg < 0 || ntiles < 0 || zero_pad_align < 0) return hipErrorInvalidValue;
+    if (nseg == 0 || ntiles == 0) return hipSuccess;
+    if (table_dev == nullptr) return hipErrorInvalidValue;
+    int blocks = (int)(ntiles > g_max_blocks ? g_max_blocks : ntiles);
+    hipLaunchKernelGGL(segcopy_kernel, dim3(blocks), dim3(LZ_BLOCK), 0,
+                       (hipStream_t)stream, (const int64_t*)table_dev, nseg,
+                       ntiles, zero_pad_align);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // fill_pattern: test/verification helper (deterministic device-side fill).
 // ---------------------------------------------------------------------------
 

@@ -49,6 +49,7 @@ import torch.distributed as dist
 
 from lzy_amd.channels.control import DriverControl, WorkerControl, broadcast_address
 from lzy_amd.channels.transport import (
+    KIND_BUNDLE,
     KIND_BYTES,
     KIND_TENSOR,
     EntryMeta,
@@ -225,7 +226,7 @@ class WorkerAgent:
                     continue
                 ops, keep = self.transport.send_ops(
                     value, self.store.pickled.get(eid), item["dst"],
-                    tag=item.get("tag", 0),
+                    tag=item.get("tag", 0), kind=item.get("kind"),
                 )
                 ops_all += ops
                 keeps.append(keep)
@@ -1083,7 +1084,8 @@ class GpuPoolRuntime(Runtime):
         pool.driver_ctrl.send(
             owner,
             {"cmd": "xfer_send_batch",
-             "items": [{"entry": entry_id, "dst": 0, "tag": xtag}]},
+             "items": [{"entry": entry_id, "dst": 0, "tag": xtag,
+                        "kind": meta.kind}]},
         )
         pool.driver_ctrl.send(
             0,
@@ -1617,13 +1619,16 @@ class _DriverScheduler:
                         # transfer's chunks on the same pair
                         xtag = pool.next_seq() % (1 << 30)
                         sends_by_owner.setdefault(owner, []).append(
-                            {"entry": eid, "dst": r, "tag": xtag}
+                            {"entry": eid, "dst": r, "tag": xtag,
+                             "kind": meta.kind}
                         )
                         recvs_by_rank.setdefault(r, []).append(
                             {"entry": eid, "src": owner,
                              "meta": meta.to_wire(), "tag": xtag}
                         )
                         METRICS.inc("lzy_transfers")
+                        if meta.kind == KIND_BUNDLE:
+                            METRICS.inc("lzy_transfers_bundle")
                     wait_entries_per_rank[r].append(eid)
                     self.transferred_now.add((r, eid))
                     meta.owners.add(r)

@@ -35,6 +35,18 @@ def _check_mode() -> bool:
     return os.environ.get("LZY_STREAM_CHECK", "") not in ("", "0")
 
 
+def _device_of(value: Any) -> Optional[torch.device]:
+    """HIP device whose stream order guards ``value``: that of a device
+    tensor, or of a tensor bundle with device leaves (channels/bundle.py —
+    one event per entry covers all its leaves); None for anything else."""
+    if isinstance(value, torch.Tensor):
+        return value.device if value.is_cuda else None
+    from lzy_amd.channels.bundle import bundle_device
+
+    dev = bundle_device(value)
+    return dev if dev is not None and dev.type == "cuda" else None
+
+
 class StreamPlacer:
     """Round-robin HIP stream pool + entry-id -> completion-event registry."""
 
@@ -94,19 +106,21 @@ class StreamPlacer:
     def record_output(self, entry_id: str, value: Any,
                       stream: Optional[torch.cuda.Stream] = None,
                       if_absent: bool = False) -> None:
-        """Record a completion event for a device-tensor entry produced on
+        """Record a completion event for a device-tensor (or device-leaf
+        tensor bundle) entry produced on
         ``stream`` (default: the current stream of the value's device).
 
         ``if_absent``: keep an existing (more precise, producer-stream)
         event — used by the blanket store-put hook, which runs on the
         publishing thread's current stream."""
-        if not self.enabled or not isinstance(value, torch.Tensor) or not value.is_cuda:
+        dev = _device_of(value) if self.enabled else None
+        if dev is None:
             return
         if if_absent:
             with self._lock:
                 if entry_id in self._events:
                     return
-        s = stream if stream is not None else torch.cuda.current_stream(value.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
         ev = torch.cuda.Event()
         ev.record(s)
         with self._lock:
@@ -120,7 +134,8 @@ class StreamPlacer:
     def wait_value(self, entry_id: str, value: Any) -> None:
         """Make the current stream wait for the entry's producing event.
         Device-side wait: does not block the host."""
-        if not self.enabled or not isinstance(value, torch.Tensor) or not value.is_cuda:
+        dev = _device_of(value) if self.enabled else None
+        if dev is None:
             return
         with self._lock:
             hit = self._events.get(entry_id)
@@ -134,7 +149,7 @@ class StreamPlacer:
                 )
             return
         ev, src_stream = hit
-        cur = torch.cuda.current_stream(value.device)
+        cur = torch.cuda.current_stream(dev)
         if cur != src_stream:
             cur.wait_event(ev)
             METRICS.inc("lzy_stream_waits_inserted")

@@ -169,7 +169,9 @@ def run_taskspec(
     live_sink=None,
 ) -> TaskResult:
     """Execute one TaskSpec against the worker store (worker innermost loop)."""
-    from lzy_amd.channels.transport import describe_value, pickle_value, unpickle_value
+    from lzy_amd.channels.transport import (
+        KIND_BYTES, describe_value, pickle_value, unpickle_value,
+    )
     from lzy_amd.snapshot import hash_value
 
     import torch
@@ -301,14 +303,16 @@ def run_taskspec(
     outputs = []
     gang_primary = spec.gang is None or spec.gang["gang_rank"] == 0
     for (eid, _), value in zip(spec.output_entries, outs):
+        # a tensor and a tensor bundle stay where they are: no D2H copy and
+        # no pickle at completion, no ``pickled=`` store entry, no inline
+        meta = describe_value(eid, value)
         pickled = None
-        if not isinstance(value, torch.Tensor):
+        if meta.kind == KIND_BYTES:
             pickled = pickle_value(value)
         from lzy_amd.runtime.streams import STREAMS as _S
 
         _S.record_output(eid, value, stream=stream)  # precise, pre-publication
         store.put(eid, value, pickled=pickled)
-        meta = describe_value(eid, value)
         wire = meta.to_wire()
         if pickled is not None:
             meta.nbytes = wire["nbytes"] = len(pickled)
