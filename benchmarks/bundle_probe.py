@@ -26,6 +26,22 @@ transformer state_dict: ``TaskResult.elapsed_s`` minus the op body, with
 bundles on (this commit) and with ``channel_bundles`` off (the pickling
 path of the parent commit), alternated.
 
+``--mode wire`` times the MXFP8 bundle wire (``bundle_wire_cast``) on the
+state_dict and on a synthetic bf16 bundle of the same segment mix, again
+alternated in one process:
+
+  * wire        ops.pack_tensors_wire(leaves, wired, out=buf)   one launch
+  * wire_kernel the same launch with the table already on the device
+  * per_leaf    what the parent commit can do: ops.mx8_pack per wired leaf
+                plus one ops.pack_tensors of the other leaves
+  * exact       ops.pack_tensors of all leaves, for context
+  * decode / decode_kernel / decode_per_leaf   the receive side likewise:
+                one ops.unpack_tensors_wire launch against ops.mx8_unpack
+                per wired leaf
+  * mx8_pack_one / mx8_unpack_one   the single-tensor kernels on ONE tensor
+                of as many elements as the wired leaves hold together: the
+                yardstick of the kernel-alone rate
+
 Prints one JSON line last.
 """
 import argparse
@@ -151,6 +167,178 @@ def _synthetic_leaves(gib: float, nseg: int = 512):
     return [pool[: n].clone() for n in sizes]
 
 
+def _synthetic_float_leaves(gib: float, nseg: int = 512):
+    """The segment mix of ``_synthetic_leaves`` as bf16 leaves (finite,
+    positive values), ``gib`` GiB in all."""
+    import random
+
+    rng = random.Random(0)
+    weights = [10 ** rng.uniform(0, 3) for _ in range(nseg)]
+    scale = gib * 2**30 / sum(weights)
+    numels = [max(1, int(w * scale) // 2) for w in weights]
+    pool = torch.empty(max(numels) + 64, dtype=torch.bfloat16, device="cuda")
+    ops.fill_pattern(pool, seed=9, mask16=0x3FFF)
+    return [pool[: n].clone() for n in numels]
+
+
+def _wire_cases(leaves):
+    from lzy_amd.channels.transport import _WIRE_MIN_ELEMS
+
+    floats = (torch.float32, torch.bfloat16, torch.float16)
+    wired = [t.dtype in floats and t.numel() >= _WIRE_MIN_ELEMS for t in leaves]
+    shapes, dtypes = [t.shape for t in leaves], [t.dtype for t in leaves]
+    numels = [t.numel() for t in leaves]
+    sizes = [t.numel() * t.element_size() for t in leaves]
+    wsizes = [ops.mx8_nbytes(n) if w else s
+              for n, s, w in zip(numels, sizes, wired)]
+    woffs, wtotal = ops.segcopy_layout(wsizes, 128)
+    offs, total = ops.segcopy_layout(sizes, 128)
+    dev = leaves[0].device
+    wbuf = torch.empty(wtotal, dtype=torch.uint8, device=dev)
+    wbuf_loop = torch.zeros(wtotal, dtype=torch.uint8, device=dev)
+    ebuf = torch.empty(total, dtype=torch.uint8, device=dev)
+    dbuf = torch.empty(total, dtype=torch.uint8, device=dev)
+    lib = ops._require_segcodec()
+
+    def wire():
+        ops.pack_tensors_wire(leaves, wired, out=wbuf)
+
+    def exact():
+        ops.pack_tensors(leaves, out=ebuf)
+
+    # the parent commit's means: one mx8_pack per wired leaf, one segcopy
+    # of the rest (into a buffer of its own: the parent has no mixed layout)
+    wired_leaves = [t for t, w in zip(leaves, wired) if w]
+    wired_out = [wbuf_loop[o: o + n] for o, n, w in zip(woffs, wsizes, wired) if w]
+    rest = [t for t, w in zip(leaves, wired) if not w]
+    rest_buf = torch.empty(
+        ops.segcopy_nbytes([t.numel() * t.element_size() for t in rest], 128),
+        dtype=torch.uint8, device=dev) if rest else None
+
+    def per_leaf():
+        for t, o in zip(wired_leaves, wired_out):
+            ops.mx8_pack(t, out=o)
+        if rest:
+            ops.pack_tensors(rest, out=rest_buf)
+
+    modes = [ops.SEGCODEC_ENCODE + ops._dtype_code(t.dtype) if w
+             else ops.SEGCODEC_RAW for t, w in zip(leaves, wired)]
+    counts = [n if w else s for n, s, w in zip(numels, sizes, wired)]
+    etab, entiles = ops.segcodec_table(
+        [t.data_ptr() for t in leaves], [wbuf.data_ptr() + o for o in woffs],
+        counts, modes)
+    etab_dev = ops._segcopy_upload(etab, dev)
+    dmodes = [ops.SEGCODEC_DECODE + ops._dtype_code(t.dtype) if w
+              else ops.SEGCODEC_RAW for t, w in zip(leaves, wired)]
+    dtab, dntiles = ops.segcodec_table(
+        [wbuf.data_ptr() + o for o in woffs], [dbuf.data_ptr() + o for o in offs],
+        counts, dmodes)
+    dtab_dev = ops._segcopy_upload(dtab, dev)
+
+    import ctypes
+
+    def _run(tab, ntiles):
+        ops._check(lib.lz_segcodec(
+            ctypes.c_void_p(tab.data_ptr()), len(leaves), ntiles, 128,
+            ctypes.c_void_p(ops._current_stream_ptr())))
+
+    def wire_kernel():
+        _run(etab_dev, entiles)
+
+    def decode():
+        ops.unpack_tensors_wire(wbuf, wired, shapes, dtypes, out=dbuf)
+
+    def decode_kernel():
+        _run(dtab_dev, dntiles)
+
+    dec_out = [torch.empty_like(t) for t in wired_leaves]
+    dec_src = [wbuf[o: o + n] for o, n, w in zip(woffs, wsizes, wired) if w]
+
+    def decode_per_leaf():
+        for s, o in zip(dec_src, dec_out):
+            ops.mx8_unpack(s, o.shape, o.dtype, out=o)
+
+    n_wired = sum(t.numel() for t in wired_leaves)
+    one = torch.empty(n_wired, dtype=wired_leaves[0].dtype, device=dev)
+    ops.fill_pattern(one, seed=4, mask16=0x3FFF)
+    one_wire = torch.empty(ops.mx8_nbytes(n_wired), dtype=torch.uint8, device=dev)
+    one_back = torch.empty_like(one)
+
+    def mx8_pack_one():
+        ops.mx8_pack(one, out=one_wire)
+
+    def mx8_unpack_one():
+        ops.mx8_unpack(one_wire, one.shape, one.dtype, out=one_back)
+
+    cases = {"wire": wire, "wire_kernel": wire_kernel, "per_leaf": per_leaf,
+             "exact": exact, "decode": decode, "decode_kernel": decode_kernel,
+             "decode_per_leaf": decode_per_leaf, "mx8_pack_one": mx8_pack_one,
+             "mx8_unpack_one": mx8_unpack_one}
+    # the two ways must agree before either is timed
+    wire()
+    per_leaf()
+    torch.cuda.synchronize()
+    for o, n, w in zip(woffs, wsizes, wired):
+        if w:
+            assert torch.equal(wbuf[o: o + n], wbuf_loop[o: o + n]), \
+                "one launch and per-leaf mx8_pack disagree"
+    decode()
+    decode_per_leaf()
+    torch.cuda.synchronize()
+    k = 0
+    for o, t, w in zip(offs, leaves, wired):
+        if w:
+            got = dbuf[o: o + t.numel() * t.element_size()]
+            assert torch.equal(got, dec_out[k].reshape(-1).view(torch.uint8)), \
+                "one-launch decode and per-leaf mx8_unpack disagree"
+            k += 1
+    wired_bytes = sum(s for s, w in zip(sizes, wired) if w)
+    wired_wire = sum(s for s, w in zip(wsizes, wired) if w)
+    rest_bytes = sum(sizes) - wired_bytes
+    # bytes read + written per case, for the GB/s column
+    moved = {
+        "wire": wired_bytes + wired_wire + 2 * rest_bytes,
+        "exact": 2 * sum(sizes),
+        "mx8_pack_one": wired_bytes + one_wire.numel(),
+    }
+    moved["wire_kernel"] = moved["per_leaf"] = moved["wire"]
+    moved["decode"] = moved["decode_kernel"] = moved["wire"]
+    moved["decode_per_leaf"] = wired_bytes + wired_wire
+    moved["mx8_unpack_one"] = moved["mx8_pack_one"]
+    info = {"segments": len(leaves), "wired_segments": len(wired_leaves),
+            "payload_mib": round(sum(sizes) / 2**20, 2),
+            "wire_mib": round(wtotal / 2**20, 2),
+            "wired_elems": n_wired}
+    return cases, moved, info
+
+
+def _report_wire(name, leaves, args):
+    cases, moved, out = _wire_cases(leaves)
+    dev, wall = _time_alternating(cases, args.iters, args.warmup)
+    for k in cases:
+        d, w = _summary(dev[k]), _summary(wall[k])
+        out[k] = {
+            "device": d, "wall": w,
+            "gb_per_s": round(moved[k] / (d["median_us"] * 1e-6) / 1e9, 1),
+        }
+        print(f"{name:10s} {k:15s} device {d['median_us']:10.1f} us "
+              f"[{d['min_us']} .. {d['max_us']}]  wall {w['median_us']:10.1f} us "
+              f"[{w['min_us']} .. {w['max_us']}]  "
+              f"{out[k]['gb_per_s']:8.1f} GB/s (read+written)")
+    return out
+
+
+def wire_mode(args) -> dict:
+    ops._require_segcodec()
+    result = {"tile_elems": ops.SEGCODEC_TILE_ELEMS}
+    model, leaves = _state_dict_leaves()
+    result["state_dict"] = _report_wire("state_dict", leaves, args)
+    del model, leaves
+    leaves = _synthetic_float_leaves(args.gib)
+    result["synthetic"] = _report_wire("synthetic", leaves, args)
+    return result
+
+
 def completion_mode(args) -> dict:
     from lzy_amd.config import Config
     from lzy_amd.runtime.taskspec import TaskSpec, WorkerStore, run_taskspec
@@ -199,7 +387,7 @@ def completion_mode(args) -> dict:
 
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["pack", "completion", "all"], default="all")
+    ap.add_argument("--mode", choices=["pack", "completion", "wire", "all"], default="all")
     ap.add_argument("--gib", type=float, default=1.0, help="synthetic bundle size")
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
@@ -221,6 +409,8 @@ def main() -> None:
         del one
     if args.mode in ("completion", "all"):
         result["completion"] = completion_mode(args)
+    if args.mode == "wire":  # "all" stays what it was
+        result["wire"] = wire_mode(args)
     print(json.dumps(result))
 
 

@@ -16,6 +16,12 @@ The receiver rebuilds the container with leaves that are views into the
 receive buffer on its own device — no unpack pass.  Rules, layout and the
 one difference from pickling (views sharing storage are packed by value):
 docs/bundles.md.
+
+With ``bundle_wire_cast="mxfp8"`` (the driver's decision, per transfer) the
+large float leaves cross the link block-scaled FP8: ``pack_bundle(value,
+wire)`` builds the wire buffer of ``bundle_wire_layout`` in one
+copy-or-codec launch, ``unpack_bundle_wire`` decodes it in one launch into
+the exact layout above and rebuilds the container from that.
 """
 from __future__ import annotations
 
@@ -175,19 +181,115 @@ def bundle_spec(value: Any) -> dict:
     return spec
 
 
-def pack_bundle(value: Any) -> torch.Tensor:
+BUNDLE_WIRES = ("", "mxfp8")
+_WIRE_DTYPE_NAMES = ("float32", "bfloat16", "float16")
+
+
+def _check_wire(wire: str) -> str:
+    if wire not in BUNDLE_WIRES:
+        raise ValueError(
+            f"bundle wire must be \"\" or \"mxfp8\", got {wire!r}"
+        )
+    return wire
+
+
+def _wired_flags(dtype_names, numels, wire: str) -> List[bool]:
+    """Leaf ``i`` is wired when its dtype is f32/bf16/f16 and it has at
+    least ``transport._WIRE_MIN_ELEMS`` elements, the threshold of every
+    other wire cast; biases, norms and every other dtype stay exact."""
+    from lzy_amd.channels.transport import _WIRE_MIN_ELEMS
+
+    if not _check_wire(wire):
+        return [False] * len(numels)
+    return [
+        name in _WIRE_DTYPE_NAMES and n >= _WIRE_MIN_ELEMS
+        for name, n in zip(dtype_names, numels)
+    ]
+
+
+def _numel(shape) -> int:
+    n = 1
+    for d in shape:
+        n *= int(d)
+    return n
+
+
+def bundle_wire_layout(spec: dict, wire: str) -> Optional[dict]:
+    """Wire form of the bundle ``spec`` under the lossy wire ``wire``:
+    ``{"wired": [bool, ...], "offsets": [int, ...], "wire_nbytes": int}``,
+    or None when ``wire`` is ``""`` or no leaf is wired — the bundle then
+    travels exact, byte for byte.  A wired leaf occupies
+    ``mx8_nbytes(numel)`` bytes (payload, then scale bytes:
+    docs/mxwire.md), an exact leaf its raw bytes; segments follow
+    ``ops.segcopy_layout(sizes, BUNDLE_ALIGN)`` in leaf order.  Reads shapes
+    and dtypes only."""
+    from lzy_amd.ops import mx8_nbytes, segcopy_layout
+
+    segs = spec["segs"]
+    numels = [_numel(s[2]) for s in segs]
+    wired = _wired_flags([s[1] for s in segs], numels, wire)
+    if not any(wired):
+        return None
+    sizes = [
+        mx8_nbytes(n) if w
+        else n * torch.empty(0, dtype=getattr(torch, s[1])).element_size()
+        for s, n, w in zip(segs, numels, wired)
+    ]
+    offsets, total = segcopy_layout(sizes, BUNDLE_ALIGN)
+    return {"wired": wired, "offsets": offsets, "wire_nbytes": total}
+
+
+def pack_bundle(value: Any, wire: str = "") -> torch.Tensor:
     """The bundle's packed ``uint8`` buffer, on the leaves' device: one
     segmented-copy launch for device leaves (a missing kernel is an error,
-    never a silent torch fallback), the torch codec for CPU leaves."""
+    never a silent torch fallback), the torch codec for CPU leaves.
+
+    With ``wire="mxfp8"`` the result is the WIRE buffer of
+    :func:`bundle_wire_layout` — large float leaves MXFP8-encoded, packed
+    by one copy-or-codec launch (``ops.pack_tensors_wire``); when no leaf
+    is wired it is the exact buffer."""
     got = _analyze(value)
     if got is None:
         raise ValueError("value is not a tensor bundle")
     leaves = got[1]
     from lzy_amd import ops
 
+    wired = _wired_flags([_dtype_name(t.dtype) for t in leaves],
+                         [t.numel() for t in leaves], wire)
+    if any(wired):
+        if leaves[0].is_cuda:
+            return ops.pack_tensors_wire(leaves, wired, align=BUNDLE_ALIGN)[0]
+        return ops.pack_tensors_wire_torch(leaves, wired, align=BUNDLE_ALIGN)[0]
     if leaves[0].is_cuda:
         return ops.pack_tensors(leaves, align=BUNDLE_ALIGN)[0]
     return ops.pack_tensors_torch(leaves, align=BUNDLE_ALIGN)[0]
+
+
+def unpack_bundle_wire(wire_buf: torch.Tensor, spec: dict, wire: str) -> Any:
+    """Rebuild the container from a ``pack_bundle(value, wire)`` buffer:
+    one decode launch (the torch codec on the CPU) into a fresh buffer of
+    ``spec["nbytes"]`` in the exact layout, every byte defined, then
+    :func:`unpack_bundle` of that — leaves are views of one allocation on
+    ``wire_buf``'s device, the wire buffer is dropped."""
+    from lzy_amd import ops
+
+    layout = bundle_wire_layout(spec, wire)
+    if layout is None:
+        return unpack_bundle(wire_buf, spec)
+    if wire_buf.numel() != layout["wire_nbytes"]:
+        raise ValueError(
+            f"bundle wire buffer has {wire_buf.numel()} bytes, "
+            f"layout says {layout['wire_nbytes']}"
+        )
+    segs = spec["segs"]
+    shapes = [s[2] for s in segs]
+    dtypes = [getattr(torch, s[1]) for s in segs]
+    decode = ops.unpack_tensors_wire if wire_buf.is_cuda \
+        else ops.unpack_tensors_wire_torch
+    buf, offsets = decode(wire_buf, layout["wired"], shapes, dtypes,
+                          align=BUNDLE_ALIGN)
+    assert offsets == [s[0] for s in segs] and buf.numel() == spec["nbytes"]
+    return unpack_bundle(buf, spec)
 
 
 def unpack_bundle(buf: torch.Tensor, spec: dict) -> Any:

@@ -340,7 +340,7 @@ class Transport:
 
     def send_ops(self, value: Any, prepickled: Optional[bytes], dst: int,
                  offset_chunks: int = 0, tag: int = 0,
-                 kind: Optional[str] = None):
+                 kind: Optional[str] = None, wire: str = ""):
         """Build send P2POps; returns (ops, keepalive).
 
         ``kind``: the entry's ``EntryMeta.kind`` when the caller knows it —
@@ -356,6 +356,10 @@ class Transport:
         FAILED transfer can never swallow a later transfer's chunks.
         NCCL/RCCL ignores tags — that path keeps the strict
         driver-sequenced issue-order discipline instead.
+
+        ``wire``: lossy wire format of a BUNDLE transfer ("" or "mxfp8"),
+        decided by the driver per transfer (``bundle_wire_cast``) and handed
+        to both endpoints; this rank's own config is not consulted.
         """
         as_bundle = kind == KIND_BUNDLE or (
             kind is None
@@ -367,10 +371,15 @@ class Transport:
             from lzy_amd.channels import bundle as _bundle
 
             # one segmented-copy launch (torch codec for CPU leaves); the
-            # packed uint8 buffer then rides the tensor path below, exact:
-            # channel_wire_cast never applies to bundles (uint8 is not a
-            # castable dtype, and the receiver never casts this kind)
-            value = _bundle.pack_bundle(value)
+            # packed uint8 buffer then rides the tensor path below as it
+            # is: channel_wire_cast never applies to bundles (uint8 is not
+            # a castable dtype, and the receiver never casts this kind).
+            # With ``wire`` (bundle_wire_cast, the driver's decision) the
+            # same launch MXFP8-encodes the large float leaves, where the
+            # leaves live: only wire bytes are staged through the host.
+            # The wire buffer is deterministic, so a resumed transfer's
+            # re-pack reproduces the chunks already delivered.
+            value = _bundle.pack_bundle(value, wire=wire)
         if isinstance(value, torch.Tensor):
             t = value.detach()
             if not t.is_contiguous():
@@ -415,24 +424,30 @@ class Transport:
         return ops, buf
 
     def recv_ops(self, meta: EntryMeta, src: int, offset_chunks: int = 0,
-                 into: Optional[torch.Tensor] = None, tag: int = 0):
+                 into: Optional[torch.Tensor] = None, tag: int = 0,
+                 wire: str = ""):
         """Build recv P2POps; returns (ops, finalize) where finalize() ->
         the received value (call after the issued works complete).
 
         ``offset_chunks``/``into`` resume into an existing buffer that
-        already holds the first ``offset_chunks`` chunks."""
+        already holds the first ``offset_chunks`` chunks (for a wired
+        bundle: of the WIRE buffer).  ``wire``: see :meth:`send_ops`."""
         if meta.kind == KIND_BUNDLE:
             # the sender's packed uint8 buffer over the tensor path (same
             # chunking, staging and tag rules, never cast); the leaves are
             # views of this one buffer on OUR device.  Follows meta.kind
             # alone — the local channel_bundles setting is not consulted.
+            # With ``wire`` the buffer on the link is the wire form; one
+            # decode launch on arrival turns it into the exact layout.
             from lzy_amd.channels import bundle as _bundle
 
             spec = meta.bundle
+            layout = _bundle.bundle_wire_layout(spec, wire)
             want_cuda = meta.device_type == "cuda" and self._device is not None
             on_device = want_cuda and self._cuda_p2p
             buf = into if into is not None else torch.empty(
-                spec["nbytes"], dtype=torch.uint8,
+                spec["nbytes"] if layout is None else layout["wire_nbytes"],
+                dtype=torch.uint8,
                 device=self._device if on_device else None,
             )
             per = self._chunk_elems(1)
@@ -448,6 +463,8 @@ class Transport:
                 out = buf
                 if want_cuda and not on_device:
                     out = out.to(self._device, non_blocking=False)
+                if layout is not None:
+                    return _bundle.unpack_bundle_wire(out, spec, wire)
                 return _bundle.unpack_bundle(out, spec)
 
             return ops, finalize_bundle
@@ -566,16 +583,17 @@ class Transport:
 
     def isend_value(self, value: Any, prepickled: Optional[bytes], dst: int,
                     offset_chunks: int = 0, tag: int = 0,
-                    kind: Optional[str] = None):
+                    kind: Optional[str] = None, wire: str = ""):
         """Issue non-blocking send(s); returns (works, keepalive)."""
         ops, keep = self.send_ops(value, prepickled, dst, offset_chunks, tag,
-                                  kind)
+                                  kind, wire)
         return self.issue(ops), keep
 
     def irecv_value(self, meta: EntryMeta, src: int, offset_chunks: int = 0,
-                    into: Optional[torch.Tensor] = None, tag: int = 0):
+                    into: Optional[torch.Tensor] = None, tag: int = 0,
+                    wire: str = ""):
         """Issue non-blocking recv; returns (works, finalize)."""
-        ops, fin = self.recv_ops(meta, src, offset_chunks, into, tag)
+        ops, fin = self.recv_ops(meta, src, offset_chunks, into, tag, wire)
         return self.issue(ops), fin
 
     @staticmethod

@@ -47,6 +47,7 @@ class Config:
     channel_chunk_mb: int = 256        # chunk size for large-tensor transfers
     channel_wire_cast: str = ""        # ""|fp16|bf16|mxfp8|fp8e4m3|fp8e5m2: lossy wire format (8-bit: prefer mxfp8, block-scaled, every path; plain fp8 is unscaled, RCCL-only)
     channel_bundles: bool = True       # dict/list/tuple nests of tensors travel as packed bundles, not pickles (docs/bundles.md)
+    bundle_wire_cast: str = ""         # ""|mxfp8: lossy wire format of bundles: f32/bf16/f16 leaves of >= 65536 elements cross ranks block-scaled FP8, other leaves exact (channel_wire_cast leaves bundles exact); the driver decides per transfer; same-rank consumers and the result cache see exact values
     stream_merge: bool = True         # fold pair_reduce trees into streamed plans
     stream_chunk_mb: int = 32          # chunk size for streamed tree plans (1 GiB shard -> 32 chunks; pipeline fill ~2 chunks per extra level)
     stream_wire_cast: str = ""         # ""|mxfp8: wire format of streamed tree plans (channel_wire_cast leaves plans exact); the driver decides per plan

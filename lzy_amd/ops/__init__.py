@@ -26,6 +26,14 @@ _MX8_AXPBY = False  # ... and lz_mx8_axpby (the fused decode-combine)
 _SEGCOPY = False  # ... and lz_segcopy (the packed-bundle gather/scatter)
 # bytes per tile of the segmented copy — LZ_SEG_TILE in hipops.hip
 SEGCOPY_TILE = 16384
+_SEGCODEC = False  # ... and lz_segcodec (segmented copy-or-MXFP8-codec)
+# elements per tile of a coded segment — LZ_SEGCODEC_ELEMS in hipops.hip
+SEGCODEC_TILE_ELEMS = 8192
+# segment modes of lz_segcodec — LZ_SC_* in hipops.hip; a coded mode is the
+# base plus the leaf's dtype code (f32 0, f16 1, bf16 2)
+SEGCODEC_RAW = 0
+SEGCODEC_ENCODE = 1
+SEGCODEC_DECODE = 4
 
 
 def _try_load() -> Optional[ctypes.CDLL]:
@@ -148,6 +156,20 @@ def _try_load() -> Optional[ctypes.CDLL]:
         _SEGCOPY = lib.lz_segcopy_tile() == SEGCOPY_TILE
     except AttributeError:
         _SEGCOPY = False
+    global _SEGCODEC
+    try:
+        lib.lz_segcodec.restype = ctypes.c_int
+        lib.lz_segcodec.argtypes = [
+            ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+            ctypes.c_void_p,
+        ]
+        lib.lz_segcodec_tile_elems.restype = ctypes.c_int
+        lib.lz_segcodec_tile_elems.argtypes = []
+        # raw segments use the segcopy tile, coded ones SEGCODEC_TILE_ELEMS
+        _SEGCODEC = _SEGCOPY and \
+            lib.lz_segcodec_tile_elems() == SEGCODEC_TILE_ELEMS
+    except AttributeError:
+        _SEGCODEC = False
     lib.lz_error_name.restype = ctypes.c_char_p
     lib.lz_error_name.argtypes = [ctypes.c_int]
     lib.lz_set_max_blocks.restype = None
@@ -651,6 +673,262 @@ def unpack_tensors(buf, offsets, shapes, dtypes, out=None):
         sizes, 0, buf.device,
     )
     return out
+
+
+# ---------------------------------------------------------------------------
+# segmented copy-or-codec: a packed buffer whose flagged ("wired") float
+# leaves are MXFP8 segments (docs/mxwire.md layout) and whose other leaves
+# are raw bytes — the wire form of a bundle under ``bundle_wire_cast``
+# ---------------------------------------------------------------------------
+
+def _require_segcodec() -> ctypes.CDLL:
+    lib = _require_native()
+    if not _SEGCODEC:
+        raise NativeExtensionMissing(
+            f"{_LIB_PATH} is stale: it lacks lz_segcodec (tile "
+            f"{SEGCODEC_TILE_ELEMS} elements); "
+            f"rebuild with `python setup.py build_ext --inplace --force`"
+        )
+    return lib
+
+
+def segcodec_table(src_addrs, dst_addrs, counts, modes,
+                   tile: int = SEGCOPY_TILE,
+                   tile_elems: int = SEGCODEC_TILE_ELEMS):
+    """The table of ``lz_segcodec`` as a flat list of ints —
+    ``src_addr[n] + dst_addr[n] + count[n] + mode[n] + tile_start[n + 1]`` —
+    and the tile count.  ``count`` is bytes for a ``SEGCODEC_RAW`` segment
+    (tiles of ``tile`` bytes) and elements for a coded one (tiles of
+    ``tile_elems`` elements); a zero-count segment owns no tile.  Pure host
+    code (no device needed)."""
+    counts = [int(n) for n in counts]
+    modes = [int(m) for m in modes]
+    if not (len(src_addrs) == len(dst_addrs) == len(counts) == len(modes)):
+        raise ValueError("segcodec_table: length mismatch")
+    tile_start = [0]
+    for n, m in zip(counts, modes):
+        if n < 0:
+            raise ValueError(f"negative segment count {n}")
+        if not SEGCODEC_RAW <= m < SEGCODEC_DECODE + 3:
+            raise ValueError(f"unknown segment mode {m}")
+        per = tile if m == SEGCODEC_RAW else tile_elems
+        tile_start.append(tile_start[-1] + (n + per - 1) // per)
+    table = [int(a) for a in src_addrs] + [int(a) for a in dst_addrs] \
+        + counts + modes + tile_start
+    return table, tile_start[-1]
+
+
+def _segcodec_launch(lib, src_addrs, dst_addrs, counts, modes,
+                     zero_pad_align: int, device) -> None:
+    import torch
+
+    table, ntiles = segcodec_table(src_addrs, dst_addrs, counts, modes)
+    if ntiles == 0:
+        return
+    dev_table = _segcopy_upload(table, device)
+    with torch.cuda.device(device):
+        _check(
+            lib.lz_segcodec(
+                ctypes.c_void_p(dev_table.data_ptr()),
+                len(counts),
+                ntiles,
+                int(zero_pad_align),
+                ctypes.c_void_p(_current_stream_ptr()),
+            )
+        )
+
+
+def _wire_sizes(numels, itemsizes, wired):
+    return [
+        mx8_nbytes(n) if w else n * isz
+        for n, isz, w in zip(numels, itemsizes, wired)
+    ]
+
+
+def _check_wired(op: str, wired, dtypes) -> list:
+    wired = [bool(w) for w in wired]
+    if len(wired) != len(dtypes):
+        raise ValueError(f"{op}: wired flags and leaves differ in length")
+    for w, dt in zip(wired, dtypes):
+        if w:
+            _mx8_check_dtype(dt, f"{op}: a wired leaf")
+    return wired
+
+
+def _check_packed_out(op: str, out, total: int, align: int, device) -> None:
+    import torch
+
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.dim() == 1
+            and out.is_contiguous()):
+        raise ValueError(f"{op}: out must be a contiguous device uint8")
+    if out.numel() != total:
+        raise ValueError(f"{op}: out has {out.numel()} bytes, expected {total}")
+    if out.device != device:
+        raise ValueError(f"{op}: out is on another device")
+    if out.data_ptr() % align:
+        raise ValueError(f"{op}: out must be {align} B-aligned")
+
+
+def _aligned_empty(total: int, align: int, device):
+    import torch
+
+    raw = torch.empty(total + align, dtype=torch.uint8, device=device)
+    skew = -raw.data_ptr() % align
+    return raw[skew: skew + total]
+
+
+def pack_tensors_wire_torch(tensors, wired, out=None, align: int = 128):
+    """Torch-only twin of :func:`pack_tensors_wire`: the codec of CPU
+    bundles and the kernel's oracle.  A wired segment is
+    ``mx8_pack_torch(leaf)``, every other byte as ``pack_tensors_torch``."""
+    import torch
+
+    from lzy_amd.channels.mxwire import mx8_pack_torch
+
+    tensors = [t.detach() for t in tensors]
+    wired = _check_wired("pack_tensors_wire_torch", wired,
+                         [t.dtype for t in tensors])
+    sizes = _wire_sizes([t.numel() for t in tensors],
+                        [t.element_size() for t in tensors], wired)
+    offsets, total = segcopy_layout(sizes, align)
+    if out is None:
+        device = tensors[0].device if tensors else None
+        out = torch.zeros(total, dtype=torch.uint8, device=device)
+    else:
+        if out.dtype != torch.uint8 or not out.is_contiguous() \
+                or out.numel() != total:
+            raise ValueError(
+                f"pack_tensors_wire_torch: out must be a contiguous uint8[{total}]"
+            )
+        out.zero_()
+    for t, w, off, n in zip(tensors, wired, offsets, sizes):
+        if n:
+            seg = mx8_pack_torch(t) if w else _byte_view(t.contiguous())
+            out[off: off + n].copy_(seg)
+    return out, offsets
+
+
+def unpack_tensors_wire_torch(wire_buf, wired, shapes, dtypes, out=None,
+                              align: int = 128):
+    """Torch-only twin of :func:`unpack_tensors_wire`: the exact-layout
+    buffer (``pack_tensors_torch`` of the decoded leaves) and its offsets."""
+    import torch
+
+    from lzy_amd.channels.mxwire import mx8_unpack_torch
+
+    shapes = [tuple(int(d) for d in s) for s in shapes]
+    wired = _check_wired("unpack_tensors_wire_torch", wired, dtypes)
+    numels = [_numel_of(s) for s in shapes]
+    itemsizes = [torch.empty(0, dtype=dt).element_size() for dt in dtypes]
+    wsizes = _wire_sizes(numels, itemsizes, wired)
+    woffs, wtotal = segcopy_layout(wsizes, align)
+    if wire_buf.dtype != torch.uint8 or wire_buf.dim() != 1 \
+            or wire_buf.numel() != wtotal:
+        raise ValueError(
+            f"unpack_tensors_wire_torch: wire buffer must be uint8[{wtotal}]"
+        )
+    leaves = []
+    for w, off, n, s, dt in zip(wired, woffs, wsizes, shapes, dtypes):
+        seg = wire_buf[off: off + n]
+        leaves.append(mx8_unpack_torch(seg, s, dt) if w
+                      else seg.clone().view(dt).view(s))
+    if not leaves:
+        return torch.zeros(0, dtype=torch.uint8, device=wire_buf.device), []
+    return pack_tensors_torch(leaves, out=out, align=align)
+
+
+def pack_tensors_wire(tensors, wired, out=None, align: int = 128):
+    """:func:`pack_tensors` with the leaves flagged in ``wired`` (f32 / bf16
+    / f16 only) MXFP8-encoded on the way: ONE segmented copy-or-codec launch
+    on the current stream.  A wired leaf occupies ``mx8_nbytes(numel)``
+    bytes, exactly what :func:`mx8_pack` writes for it; the other leaves,
+    the layout rule (``segcopy_layout`` of the wire sizes), the zeroed gaps
+    and ``out`` are as for :func:`pack_tensors`.  Returns
+    ``(buf, offsets)``."""
+    import torch
+
+    tensors = [t.detach() if t.requires_grad else t for t in tensors]
+    align = _check_align(align)
+    if not tensors:
+        raise ValueError("pack_tensors_wire: no tensors")
+    wired = _check_wired("pack_tensors_wire", wired,
+                         [t.dtype for t in tensors])
+    device = tensors[0].device
+    for t in tensors:
+        if not t.is_cuda:
+            raise ValueError("pack_tensors_wire requires device tensors")
+        if t.device != device:
+            raise ValueError(
+                f"pack_tensors_wire: leaves on different devices "
+                f"({device}, {t.device})"
+            )
+    numels = [t.numel() for t in tensors]
+    sizes = _wire_sizes(numels, [t.element_size() for t in tensors], wired)
+    offsets, total = segcopy_layout(sizes, align)
+    if out is not None:
+        _check_packed_out("pack_tensors_wire", out, total, align, device)
+    lib = _require_segcodec()
+    if out is None:
+        out = _aligned_empty(total, align, device)
+    srcs = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    base = out.data_ptr()
+    _segcodec_launch(
+        lib, [s.data_ptr() for s in srcs], [base + o for o in offsets],
+        [n if w else sz for n, sz, w in zip(numels, sizes, wired)],
+        [SEGCODEC_ENCODE + _dtype_code(t.dtype) if w else SEGCODEC_RAW
+         for t, w in zip(tensors, wired)],
+        align, device,
+    )
+    return out, offsets
+
+
+def unpack_tensors_wire(wire_buf, wired, shapes, dtypes, out=None,
+                        align: int = 128):
+    """Decode a :func:`pack_tensors_wire` buffer into the EXACT packed
+    layout (what :func:`pack_tensors` of the decoded leaves would give,
+    every byte defined) with one launch; returns ``(buf, offsets)``, so the
+    leaves are ``unpack_tensors(buf, offsets, shapes, dtypes)`` views of one
+    allocation.  ``out``: as for :func:`pack_tensors`."""
+    import torch
+
+    align = _check_align(align)
+    shapes = [tuple(int(d) for d in s) for s in shapes]
+    wired = _check_wired("unpack_tensors_wire", wired, dtypes)
+    if len(shapes) != len(wired):
+        raise ValueError("unpack_tensors_wire: shapes/dtypes differ in length")
+    if not shapes:
+        raise ValueError("unpack_tensors_wire: no tensors")
+    if not (wire_buf.is_cuda and wire_buf.dtype == torch.uint8
+            and wire_buf.dim() == 1 and wire_buf.is_contiguous()):
+        raise ValueError(
+            "unpack_tensors_wire: wire buffer must be a contiguous device uint8"
+        )
+    numels = [_numel_of(s) for s in shapes]
+    itemsizes = [torch.empty(0, dtype=dt).element_size() for dt in dtypes]
+    wsizes = _wire_sizes(numels, itemsizes, wired)
+    woffs, wtotal = segcopy_layout(wsizes, align)
+    if wire_buf.numel() != wtotal:
+        raise ValueError(
+            f"unpack_tensors_wire: wire buffer has {wire_buf.numel()} bytes, "
+            f"expected {wtotal}"
+        )
+    sizes = [n * isz for n, isz in zip(numels, itemsizes)]
+    offsets, total = segcopy_layout(sizes, align)
+    device = wire_buf.device
+    if out is not None:
+        _check_packed_out("unpack_tensors_wire", out, total, align, device)
+    lib = _require_segcodec()
+    if out is None:
+        out = _aligned_empty(total, align, device)
+    sbase, dbase = wire_buf.data_ptr(), out.data_ptr()
+    _segcodec_launch(
+        lib, [sbase + o for o in woffs], [dbase + o for o in offsets],
+        [n if w else sz for n, sz, w in zip(numels, sizes, wired)],
+        [SEGCODEC_DECODE + _dtype_code(dt) if w else SEGCODEC_RAW
+         for dt, w in zip(dtypes, wired)],
+        align, device,
+    )
+    return out, offsets
 
 
 def device_checksum(t, method: str = "auto") -> int:

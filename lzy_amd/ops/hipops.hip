@@ -354,10 +354,73 @@ mx8_pack_kernel(const T* __restrict__ src, uint8_t* __restrict__ dst, int64_t n)
     }
 }
 
+// one group (8 elements) of the decode, in two steps so that a caller with
+// several groups per lane can issue every load before the first store.
+// Step 1: the group's payload words and its block's scale byte.
+template <bool ALIGNED>
+__device__ __forceinline__ void lz_mx8_dec_load(const uint8_t* __restrict__ src,
+                                                const uint8_t* __restrict__ scales,
+                                                int64_t g, uint32_t (&w)[2],
+                                                uint32_t& b) {
+    const int64_t e0 = g * 8;
+    if (ALIGNED) {
+        LzVec8 pv = *reinterpret_cast<const LzVec8*>(src + e0);
+        w[0] = pv.w[0];
+        w[1] = pv.w[1];
+    } else {
+        w[0] = w[1] = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            w[0] |= (uint32_t)src[e0 + k] << (8 * k);
+            w[1] |= (uint32_t)src[e0 + 4 + k] << (8 * k);
+        }
+    }
+    b = scales[g >> 2];
+}
+
+// Step 2: dequantize and store the elements of the group that lie in [0, n).
+//
+// SIGNED_ZERO: for f16 the compiler folds the multiply and the convert into
+// one v_fma_mixlo_f16 (q * mult + 0), and -0 + 0 is +0: a negative-zero
+// payload byte, or a negative value that underflows f16, comes out +0.0
+// where the reference codec gives -0.0.  mx8_unpack_kernel keeps that
+// (equal as values; its callers compare values); the bundle decode is held
+// to the reference byte for byte and puts the sign back.
+template <typename T, bool ALIGNED, bool SIGNED_ZERO = false>
+__device__ __forceinline__ void lz_mx8_dec_store(const uint32_t (&w)[2], uint32_t b,
+                                                 T* __restrict__ dst, int64_t g,
+                                                 int64_t n) {
+    constexpr int V = 8;
+    const int64_t e0 = g * V;
+    const float mult = __uint_as_float(b ? (b << 23) : 0x00400000u);
+    T y[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        __hip_fp8_e4m3 q;
+        q.__x = (__hip_fp8_storage_t)(w[k >> 2] >> (8 * (k & 3)));
+        const float v = float(q) * mult;
+        y[k] = lz_from_float<T>(v);
+        if constexpr (SIGNED_ZERO && std::is_same<T, __half>::value)
+            y[k] = __ushort_as_half((unsigned short)(
+                (__half_as_ushort(y[k]) & 0x7fffu) |
+                ((__float_as_uint(v) >> 16) & 0x8000u)));
+    }
+    if (ALIGNED && e0 + V <= n) {
+        LzVec16 q[sizeof(T) * V / 16];
+        __builtin_memcpy(q, y, sizeof(y));
+        LzVec16* p = reinterpret_cast<LzVec16*>(dst + e0);
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(T) * V / 16); ++k) p[k] = q[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            if (e0 + k < n) dst[e0 + k] = y[k];
+    }
+}
+
 template <typename T, bool ALIGNED>
 __global__ void __launch_bounds__(LZ_BLOCK)
 mx8_unpack_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst, int64_t n) {
-    constexpr int V = 8;
     const int64_t nblk = (n + 31) >> 5;
     const int64_t ngroups = nblk * 4;
     const uint8_t* __restrict__ scales = src + nblk * 32;
@@ -365,41 +428,10 @@ mx8_unpack_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst, int64_t 
 
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups;
          g += stride) {
-        const int64_t e0 = g * V;
-        if (e0 >= n) continue;  // padded tail of the last block
-        uint32_t w[2];
-        if (ALIGNED) {
-            LzVec8 pv = *reinterpret_cast<const LzVec8*>(src + e0);
-            w[0] = pv.w[0];
-            w[1] = pv.w[1];
-        } else {
-            w[0] = w[1] = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                w[0] |= (uint32_t)src[e0 + k] << (8 * k);
-                w[1] |= (uint32_t)src[e0 + 4 + k] << (8 * k);
-            }
-        }
-        const uint32_t b = scales[g >> 2];
-        const float mult = __uint_as_float(b ? (b << 23) : 0x00400000u);
-        T y[V];
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            __hip_fp8_e4m3 q;
-            q.__x = (__hip_fp8_storage_t)(w[k >> 2] >> (8 * (k & 3)));
-            y[k] = lz_from_float<T>(float(q) * mult);
-        }
-        if (ALIGNED && e0 + V <= n) {
-            LzVec16 q[sizeof(T) * V / 16];
-            __builtin_memcpy(q, y, sizeof(y));
-            LzVec16* p = reinterpret_cast<LzVec16*>(dst + e0);
-#pragma unroll
-            for (int k = 0; k < (int)(sizeof(T) * V / 16); ++k) p[k] = q[k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < V; ++k)
-                if (e0 + k < n) dst[e0 + k] = y[k];
-        }
+        if (g * 8 >= n) continue;  // padded tail of the last block
+        uint32_t w[2], b;
+        lz_mx8_dec_load<ALIGNED>(src, scales, g, w, b);
+        lz_mx8_dec_store<T, ALIGNED>(w, b, dst, g, n);
     }
 }
 
@@ -1503,6 +1535,220 @@ extern "C" hipError_t lz_segcopy(const void* table_dev, int64_t nseg,
     if (table_dev == nullptr) return hipErrorInvalidValue;
     int blocks = (int)(ntiles > g_max_blocks ? g_max_blocks : ntiles);
     hipLaunchKernelGGL(segcopy_kernel, dim3(blocks), dim3(LZ_BLOCK), 0,
+                       (hipStream_t)stream, (const int64_t*)table_dev, nseg,
+                       ntiles, zero_pad_align);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// segcodec: segcopy whose segments may also be MXFP8-encoded or -decoded on
+// the way — a tensor bundle whose large float leaves cross the wire
+// block-scaled (bundle_wire_cast, docs/bundles.md) is packed by ONE launch
+// and decoded into the exact bundle layout by ONE launch.
+// ---------------------------------------------------------------------------
+//
+// Table (int64, device memory): src_addr[nseg], dst_addr[nseg], count[nseg],
+// mode[nseg], tile_start[nseg + 1].
+//   mode LZ_SC_RAW          copy `count` BYTES, tiles of LZ_SEG_TILE bytes
+//                           (the body of segcopy_kernel);
+//   mode LZ_SC_ENC + dtype  src: `count` ELEMENTS of f32/f16/bf16 (LzDtype
+//                           0/1/2), dst: their mx8 buffer, 33*nblk bytes;
+//   mode LZ_SC_DEC + dtype  src: an mx8 buffer, dst: `count` elements.
+// A coded segment's tiles are LZ_SEGCODEC_ELEMS elements: tile t owns
+// elements [t*E, min((t+1)*E, n)), payload bytes at seg + t*E and scale bytes
+// at seg + 32*nblk + t*E/32.  E is a multiple of LZ_BLOCK*8, so a tile is a
+// whole number of sweeps of the workgroup at one 8-element group per lane,
+// the 4 lanes of a block are an aligned quad as in mx8_pack_kernel, and
+// E/32 is a multiple of 64: the 4-byte scale stores of lz_mx8_emit stay
+// aligned and never straddle tiles.  A wired segment is therefore the bytes
+// lz_mx8_pack writes for the same leaf (same device functions, and a block's
+// bytes depend on the block's elements alone).  The decode is the body of
+// mx8_unpack_kernel with the sign of an f16 zero kept (lz_mx8_dec_store,
+// SIGNED_ZERO), which makes it byte-identical to the torch codec.
+//
+// Segment, mode and alignment class are functions of blockIdx and the table
+// only: wave-uniform.  Every wave of the workgroup walks its groups with a
+// wave-uniform bound, so the DPP steps of lz_mx8_emit run with all 64 lanes
+// on; the guards sit inside emit.  Fast path: the tile lies wholly inside
+// the leaf, the leaf is 16 B-aligned and the mx8 side 8 B-aligned (segments
+// of a packed buffer are 128 B-aligned, so only a misaligned source VIEW
+// falls off it) — every load of the tile is issued before the first store.
+// Anything else, and each segment's last tile, takes the guarded path.
+//
+// Nothing before or past a source is read.  Encode writes the whole mx8
+// buffer, 0x00 for the padded payload of the last block; decode writes the
+// n elements.  With zero_pad_align > 0 the segment's last tile zero-fills
+// from the end of what it wrote to the next multiple, as segcopy does.
+// Nothing else is written.  Zero-count segments own no tile.
+#ifndef LZ_SEGCODEC_ELEMS
+#define LZ_SEGCODEC_ELEMS 8192
+#endif
+static_assert(LZ_SEGCODEC_ELEMS % (LZ_BLOCK * 8) == 0, "tile = whole group sweeps");
+
+#define LZ_SC_RAW 0
+#define LZ_SC_ENC 1  // + LzDtype (f32/f16/bf16): 1, 2, 3
+#define LZ_SC_DEC 4  // + LzDtype: 4, 5, 6
+
+extern "C" int lz_segcodec_tile_elems() { return LZ_SEGCODEC_ELEMS; }
+
+// zero [end, align_up(end, a)) — one workgroup
+__device__ __forceinline__ void lz_seg_zero_pad(uint64_t end, int zero_pad_align) {
+    const uint64_t a = (uint64_t)zero_pad_align;
+    const int pad = (int)((end + a - 1) / a * a - end);
+    LZ_GLOBAL uint8_t* p = (LZ_GLOBAL uint8_t*)end;
+    for (int i = (int)threadIdx.x; i < pad; i += LZ_BLOCK) p[i] = 0;
+}
+
+// The table's addresses become global-address-space pointers first (see
+// LZ_GLOBAL above); the generic pointers the mx8 device functions take are
+// casts of those, which the compiler folds back once they are inlined.
+template <typename T>
+__device__ __forceinline__ void lz_segcodec_encode_tile(uint64_t sa, uint64_t da,
+                                                        int64_t n, int64_t tix) {
+    constexpr int U = LZ_SEGCODEC_ELEMS / (LZ_BLOCK * 8);  // groups per lane
+    constexpr int64_t TG = LZ_SEGCODEC_ELEMS / 8;          // groups per tile
+    const T* __restrict__ src = (const T*)(const LZ_GLOBAL T*)sa;
+    uint8_t* __restrict__ dst = (uint8_t*)(LZ_GLOBAL uint8_t*)da;
+    const int64_t nblk = (n + 31) >> 5;
+    const int64_t ngroups = nblk * 4;
+    uint8_t* __restrict__ scales = dst + nblk * 32;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t gtile = tix * TG;
+    const bool src_al = (sa & 15u) == 0, dst_al = (da & 7u) == 0;
+
+    if (src_al && dst_al && (gtile + TG) * 8 <= n) {
+        float f[U][8];
+#pragma unroll
+        for (int k = 0; k < U; ++k)
+            lz_mx8_load<T, true>(src, (gtile + k * LZ_BLOCK + wave * 64 + lane) * 8,
+                                 n, f[k]);
+#pragma unroll
+        for (int k = 0; k < U; ++k)
+            lz_mx8_emit<true, true>(f[k], gtile + k * LZ_BLOCK + wave * 64 + lane,
+                                    lane, ngroups, nblk, dst, scales);
+        return;
+    }
+    // g0, the group of the wave's lane 0, and the bound on it are
+    // wave-uniform: emit's cross-lane steps see all 64 lanes
+    for (int k = 0; k < U; ++k) {
+        const int64_t g0 = gtile + k * LZ_BLOCK + wave * 64;
+        if (g0 >= ngroups) break;
+        const int64_t g = g0 + lane;
+        float f[8];
+        lz_mx8_load<T, false>(src, g * 8, n, f);
+        if (dst_al) lz_mx8_emit<true, false>(f, g, lane, ngroups, nblk, dst, scales);
+        else lz_mx8_emit<false, false>(f, g, lane, ngroups, nblk, dst, scales);
+    }
+}
+
+template <typename T, bool ALIGNED>
+__device__ __forceinline__ void lz_segcodec_decode_groups(
+    const uint8_t* __restrict__ src, const uint8_t* __restrict__ scales,
+    T* __restrict__ dst, int64_t n, int64_t gtile) {
+    constexpr int U = LZ_SEGCODEC_ELEMS / (LZ_BLOCK * 8);
+    uint32_t w[U][2], b[U];
+    // a group past the end re-reads the segment's first group (inside the
+    // source whenever the segment owns a tile) and stores nothing
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+        const int64_t g = gtile + k * LZ_BLOCK + (int)threadIdx.x;
+        lz_mx8_dec_load<ALIGNED>(src, scales, g * 8 < n ? g : 0, w[k], b[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+        const int64_t g = gtile + k * LZ_BLOCK + (int)threadIdx.x;
+        if (g * 8 < n) lz_mx8_dec_store<T, ALIGNED, true>(w[k], b[k], dst, g, n);
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void lz_segcodec_decode_tile(uint64_t sa, uint64_t da,
+                                                        int64_t n, int64_t tix) {
+    const uint8_t* __restrict__ src = (const uint8_t*)(const LZ_GLOBAL uint8_t*)sa;
+    T* __restrict__ dst = (T*)(LZ_GLOBAL T*)da;
+    const int64_t nblk = (n + 31) >> 5;
+    const uint8_t* __restrict__ scales = src + nblk * 32;
+    const int64_t gtile = tix * (LZ_SEGCODEC_ELEMS / 8);
+    if ((sa & 7u) == 0 && (da & 15u) == 0)
+        lz_segcodec_decode_groups<T, true>(src, scales, dst, n, gtile);
+    else
+        lz_segcodec_decode_groups<T, false>(src, scales, dst, n, gtile);
+}
+
+__global__ void __launch_bounds__(LZ_BLOCK)
+segcodec_kernel(const int64_t* __restrict__ table, int64_t nseg, int64_t ntiles,
+                int zero_pad_align) {
+    const int64_t* __restrict__ src_addr = table;
+    const int64_t* __restrict__ dst_addr = table + nseg;
+    const int64_t* __restrict__ seg_count = table + 2 * nseg;
+    const int64_t* __restrict__ seg_mode = table + 3 * nseg;
+    const int64_t* __restrict__ tile_start = table + 4 * nseg;
+
+    int64_t lo = 0;  // a block's tiles ascend, so its segment index does too
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        // the search of segcopy_kernel
+        if (tile >= tile_start[lo + 1]) {
+            int64_t hi = nseg;
+            while (hi - lo > 1) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (tile_start[mid] <= tile) lo = mid; else hi = mid;
+            }
+        }
+        const int64_t cnt = seg_count[lo];
+        const int mode = (int)seg_mode[lo];
+        const int64_t tix = tile - tile_start[lo];
+        const uint64_t sbase = (uint64_t)src_addr[lo];
+        const uint64_t dbase = (uint64_t)dst_addr[lo];
+
+        if (mode == LZ_SC_RAW) {
+            const int64_t off = tix * (int64_t)LZ_SEG_TILE;
+            const int64_t rest = cnt - off;
+            if (rest <= 0) continue;  // malformed table: never index past a segment
+            const int len = (int)(rest < LZ_SEG_TILE ? rest : LZ_SEG_TILE);
+            const uint64_t sa = sbase + (uint64_t)off;
+            const uint64_t da = dbase + (uint64_t)off;
+            const unsigned mis = (unsigned)((sa | da) & 15u);
+            if (mis == 0) lz_seg_tile_copy<lz_u32x4>(sa, da, len);
+            else if ((mis & 7u) == 0) lz_seg_tile_copy<lz_u32x2>(sa, da, len);
+            else if ((mis & 3u) == 0) lz_seg_tile_copy<uint32_t>(sa, da, len);
+            else if ((mis & 1u) == 0) lz_seg_tile_copy<uint16_t>(sa, da, len);
+            else lz_seg_tile_copy<uint8_t>(sa, da, len);
+            if (zero_pad_align > 0 && rest <= LZ_SEG_TILE)  // segment's last tile
+                lz_seg_zero_pad(dbase + (uint64_t)cnt, zero_pad_align);
+            continue;
+        }
+        const int64_t rest = cnt - tix * (int64_t)LZ_SEGCODEC_ELEMS;
+        if (rest <= 0) continue;  // malformed table
+        const bool last = rest <= LZ_SEGCODEC_ELEMS;
+        const int64_t nblk = (cnt + 31) >> 5;
+        switch (mode) {
+            case LZ_SC_ENC + LZ_F32: lz_segcodec_encode_tile<float>(sbase, dbase, cnt, tix); break;
+            case LZ_SC_ENC + LZ_F16: lz_segcodec_encode_tile<__half>(sbase, dbase, cnt, tix); break;
+            case LZ_SC_ENC + LZ_BF16: lz_segcodec_encode_tile<__hip_bfloat16>(sbase, dbase, cnt, tix); break;
+            case LZ_SC_DEC + LZ_F32: lz_segcodec_decode_tile<float>(sbase, dbase, cnt, tix); break;
+            case LZ_SC_DEC + LZ_F16: lz_segcodec_decode_tile<__half>(sbase, dbase, cnt, tix); break;
+            case LZ_SC_DEC + LZ_BF16: lz_segcodec_decode_tile<__hip_bfloat16>(sbase, dbase, cnt, tix); break;
+            default: continue;  // malformed table: touch nothing
+        }
+        if (zero_pad_align > 0 && last) {
+            const int64_t wrote = mode < LZ_SC_DEC ? 33 * nblk
+                : cnt * (mode == LZ_SC_DEC + LZ_F32 ? 4 : 2);
+            lz_seg_zero_pad(dbase + (uint64_t)wrote, zero_pad_align);
+        }
+    }
+}
+
+// As lz_segcopy: the caller owns the device table and has ordered its upload
+// before this launch on ``stream``.
+extern "C" hipError_t lz_segcodec(const void* table_dev, int64_t nseg,
+                                  int64_t ntiles, int zero_pad_align,
+                                  void* stream) {
+    if (nseg < 0 || ntiles < 0 || zero_pad_align < 0) return hipErrorInvalidValue;
+    if (nseg == 0 || ntiles == 0) return hipSuccess;
+    if (table_dev == nullptr) return hipErrorInvalidValue;
+    int blocks = (int)(ntiles > g_max_blocks ? g_max_blocks : ntiles);
+    hipLaunchKernelGGL(segcodec_kernel, dim3(blocks), dim3(LZ_BLOCK), 0,
                        (hipStream_t)stream, (const int64_t*)table_dev, nseg,
                        ntiles, zero_pad_align);
     return hipGetLastError();

@@ -227,6 +227,7 @@ class WorkerAgent:
                 ops, keep = self.transport.send_ops(
                     value, self.store.pickled.get(eid), item["dst"],
                     tag=item.get("tag", 0), kind=item.get("kind"),
+                    wire=item.get("wire", ""),
                 )
                 ops_all += ops
                 keeps.append(keep)
@@ -245,7 +246,8 @@ class WorkerAgent:
             for item in msg["items"]:
                 meta = EntryMeta.from_wire(item["meta"])
                 ops, fin = self.transport.recv_ops(
-                    meta, item["src"], tag=item.get("tag", 0)
+                    meta, item["src"], tag=item.get("tag", 0),
+                    wire=item.get("wire", ""),
                 )
                 fins.append((item["entry"], len(ops), fin))
                 ops_all += ops
@@ -1081,22 +1083,55 @@ class GpuPoolRuntime(Runtime):
         if owner is None:
             return
         xtag = pool.next_seq() % (1 << 30)
+        send_item = {"entry": entry_id, "dst": 0, "tag": xtag,
+                     "kind": meta.kind}
+        recv_item = {"entry": entry_id, "src": owner,
+                     "meta": meta.to_wire(), "tag": xtag}
+        if meta.kind == KIND_BUNDLE:
+            # the driver-side read is a transfer like any other (the config
+            # resolve is kept off the bare-tensor fetch path)
+            from lzy_amd.config import get_config
+
+            _wire_bundle_items(
+                meta, _bundle_wire_cast(get_config()), send_item, recv_item
+            )
         pool.driver_ctrl.send(
-            owner,
-            {"cmd": "xfer_send_batch",
-             "items": [{"entry": entry_id, "dst": 0, "tag": xtag,
-                        "kind": meta.kind}]},
+            owner, {"cmd": "xfer_send_batch", "items": [send_item]},
         )
         pool.driver_ctrl.send(
-            0,
-            {"cmd": "xfer_recv_batch",
-             "items": [{"entry": entry_id, "src": owner,
-                        "meta": meta.to_wire(), "tag": xtag}]},
+            0, {"cmd": "xfer_recv_batch", "items": [recv_item]},
         )
         tag = f"f{pool.next_seq()}"
         pool.driver_ctrl.send(0, {"cmd": "settle", "entries": [entry_id], "tag": tag})
         pool.wait_acks("settled", tag, [0])
         meta.owners.add(0)
+
+
+def _bundle_wire_cast(cfg) -> str:
+    """The validated ``bundle_wire_cast`` setting of ``cfg``."""
+    wire = str(getattr(cfg, "bundle_wire_cast", "") or "")
+    if wire not in ("", "mxfp8"):
+        raise ValueError(
+            f"bundle_wire_cast must be \"\" or \"mxfp8\", got {wire!r}"
+        )
+    return wire
+
+
+def _wire_bundle_items(meta: EntryMeta, wire: str, send_item: dict,
+                       recv_item: dict) -> int:
+    """The driver's decision for one transfer: when ``meta`` is a bundle
+    with at least one leaf the wire ``wire`` encodes, mark BOTH items
+    (``"wire"`` is a key of the item, never of ``EntryMeta.to_wire()``) so
+    sender and receiver cannot disagree.  Returns the bytes on the link."""
+    if wire and meta.kind == KIND_BUNDLE:
+        from lzy_amd.channels.bundle import bundle_wire_layout
+
+        layout = bundle_wire_layout(meta.bundle, wire)
+        if layout is not None:
+            send_item["wire"] = recv_item["wire"] = wire
+            METRICS.inc("lzy_transfers_bundle_wired")
+            return layout["wire_nbytes"]
+    return meta.nbytes
 
 
 class _DriverScheduler:
@@ -1184,6 +1219,9 @@ class _DriverScheduler:
                 f"stream_wire_cast must be \"\" or \"mxfp8\", "
                 f"got {self._stream_wire!r}"
             )
+        # wire format of tensor bundles (docs/bundles.md): again the
+        # driver's decision, carried by the transfer items
+        self._bundle_wire = _bundle_wire_cast(cfg)
         # explicit ipc mode, or automatic when ranks outnumber GPUs:
         # RCCL cannot build a comm then, and the host-staged fallback is
         # ~19x slower than hipIpc zero-copy for device tensors on one
@@ -1602,6 +1640,7 @@ class _DriverScheduler:
                     ]
                     pickable = confirmed or sorted(meta.owners)
                     owner = 0 if 0 in pickable else pickable[0]
+                    link_bytes = meta.nbytes
                     if use_ipc:
                         # zero-copy path: map the producer's HBM allocation
                         # in the consumer (hipIpc; same GPU = no copy,
@@ -1618,21 +1657,22 @@ class _DriverScheduler:
                         # posted recvs can never swallow a later
                         # transfer's chunks on the same pair
                         xtag = pool.next_seq() % (1 << 30)
-                        sends_by_owner.setdefault(owner, []).append(
-                            {"entry": eid, "dst": r, "tag": xtag,
-                             "kind": meta.kind}
+                        send_item = {"entry": eid, "dst": r, "tag": xtag,
+                                     "kind": meta.kind}
+                        recv_item = {"entry": eid, "src": owner,
+                                     "meta": meta.to_wire(), "tag": xtag}
+                        link_bytes = _wire_bundle_items(
+                            meta, self._bundle_wire, send_item, recv_item
                         )
-                        recvs_by_rank.setdefault(r, []).append(
-                            {"entry": eid, "src": owner,
-                             "meta": meta.to_wire(), "tag": xtag}
-                        )
+                        sends_by_owner.setdefault(owner, []).append(send_item)
+                        recvs_by_rank.setdefault(r, []).append(recv_item)
                         METRICS.inc("lzy_transfers")
                         if meta.kind == KIND_BUNDLE:
                             METRICS.inc("lzy_transfers_bundle")
                     wait_entries_per_rank[r].append(eid)
                     self.transferred_now.add((r, eid))
                     meta.owners.add(r)
-                    METRICS.inc("lzy_transfer_bytes", meta.nbytes)
+                    METRICS.inc("lzy_transfer_bytes", link_bytes)
                 elif (r, eid) in self.transferred_now:
                     # transfer already initiated for an earlier task this
                     # batch; this task must still wait for its settle
