@@ -1,12 +1,18 @@
 """Byte-rate probe for the block-scaled FP8 (mxfp8) wire kernels (run on
 an MI355X).
 
-On a 1 GiB bf16 buffer, times in one process, interleaved round-robin:
+On a 1 GiB bf16 buffer (``--dtype f16`` / ``f32``: as many bytes of that
+type), times in one process, interleaved round-robin:
 
   * ops.mx8_pack     bf16 -> mxfp8 wire      (reads 2 B, writes 33/32 B / elem)
   * ops.mx8_unpack   mxfp8 wire -> bf16
   * ops.cast_copy    bf16 -> fp8e4m3         (the yardstick: reads 2 B, writes 1 B)
   * ops.cast_copy    fp8e4m3 -> bf16
+
+``--compare-lib PATH`` adds the ``lz_mx8_pack`` and ``lz_mx8_unpack`` of
+another build of libhipops.so (say, the parent commit's) to the same rounds,
+on the same source buffers, so that two builds are compared call by call in
+one process.
 
 Each call is timed with device events; the figure reported is
 (bytes read + bytes written) / median time.  Also reports the fraction of
@@ -25,6 +31,7 @@ the two in one process:
 and checks that both give the same values to one unit in the last place.
 """
 import argparse
+import ctypes
 import json
 import statistics
 import sys
@@ -116,12 +123,20 @@ def axpby_mode(args) -> None:
     print(json.dumps(result))
 
 
+_DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["codec", "axpby"], default="codec")
     ap.add_argument("--melems", type=int, default=64,
                     help="axpby mode: Mi elements per buffer")
-    ap.add_argument("--mib", type=int, default=1024, help="bf16 buffer size")
+    ap.add_argument("--mib", type=int, default=1024, help="tensor buffer size")
+    ap.add_argument("--dtype", choices=sorted(_DTYPES), default="bf16",
+                    help="codec mode: element type of the tensor side")
+    ap.add_argument("--compare-lib", default=None,
+                    help="codec mode: another build of libhipops.so whose "
+                         "lz_mx8_unpack is timed in the same rounds")
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     args = ap.parse_args()
@@ -131,22 +146,51 @@ def main() -> None:
     if args.mode == "axpby":
         axpby_mode(args)
         return
-    n = (args.mib << 20) // 2
-    src = torch.empty(n, device="cuda", dtype=torch.bfloat16)
-    ops.fill_pattern(src, seed=3, mask16=0x3FFF)  # finite positive bf16
+    dtype, dname = _DTYPES[args.dtype], args.dtype
+    es = torch.empty(0, dtype=dtype).element_size()
+    n = (args.mib << 20) // es
+    src = torch.empty(n, device="cuda", dtype=dtype)
+    # every 16-bit lane <= 0x3FFF: finite and positive in all three types
+    ops.fill_pattern(src, seed=3, mask16=0x3FFF)
     wire = torch.empty(ops.mx8_nbytes(n), device="cuda", dtype=torch.uint8)
     fp8 = torch.empty(n, device="cuda", dtype=torch.float8_e4m3fn)
-    back = torch.empty(n, device="cuda", dtype=torch.bfloat16)
+    back = torch.empty(n, device="cuda", dtype=dtype)
     ops.mx8_pack(src, out=wire)
     ops.cast_copy(src, fp8)
 
     cases = {
-        "mx8_pack": (lambda: ops.mx8_pack(src, out=wire), 2 * n + wire.numel()),
-        "mx8_unpack": (lambda: ops.mx8_unpack(wire, n, torch.bfloat16, out=back),
-                       wire.numel() + 2 * n),
-        "cast_bf16_to_e4m3": (lambda: ops.cast_copy(src, fp8), 2 * n + n),
-        "cast_e4m3_to_bf16": (lambda: ops.cast_copy(fp8, back), n + 2 * n),
+        "mx8_pack": (lambda: ops.mx8_pack(src, out=wire), es * n + wire.numel()),
+        "mx8_unpack": (lambda: ops.mx8_unpack(wire, n, dtype, out=back),
+                       wire.numel() + es * n),
+        f"cast_{dname}_to_e4m3": (lambda: ops.cast_copy(src, fp8), es * n + n),
+        f"cast_e4m3_to_{dname}": (lambda: ops.cast_copy(fp8, back), n + es * n),
     }
+    if args.compare_lib:
+        other = ctypes.CDLL(args.compare_lib)
+        other.lz_mx8_unpack.restype = ctypes.c_int
+        other.lz_mx8_unpack.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_int, ctypes.c_int64,
+                                        ctypes.c_void_p]
+        other.lz_mx8_pack.restype = ctypes.c_int
+        other.lz_mx8_pack.argtypes = [ctypes.c_void_p, ctypes.c_int,
+                                      ctypes.c_void_p, ctypes.c_int64,
+                                      ctypes.c_void_p]
+        back2 = torch.empty_like(back)
+        wire2 = torch.empty_like(wire)
+        code = ops._dtype_code(dtype)
+
+        def other_pack():
+            err = other.lz_mx8_pack(src.data_ptr(), code, wire2.data_ptr(), n,
+                                    ops._current_stream_ptr())
+            assert err == 0, err
+
+        def other_unpack():
+            err = other.lz_mx8_unpack(wire.data_ptr(), back2.data_ptr(), code, n,
+                                      ops._current_stream_ptr())
+            assert err == 0, err
+
+        cases["mx8_pack@compare-lib"] = (other_pack, es * n + wire.numel())
+        cases["mx8_unpack@compare-lib"] = (other_unpack, wire.numel() + es * n)
     for _ in range(args.warmup):
         for fn, _b in cases.values():
             fn()
@@ -163,7 +207,16 @@ def main() -> None:
             e1.synchronize()
             times[name].append(e0.elapsed_time(e1) * 1e-3)
 
-    result = {"buffer_mib": args.mib, "iters": args.iters}
+    result = {"buffer_mib": args.mib, "dtype": dname, "iters": args.iters}
+    if args.compare_lib:
+        ops.mx8_unpack(wire, n, dtype, out=back)
+        other_unpack()
+        torch.cuda.synchronize()
+        bits = torch.int32 if es == 4 else torch.int16
+        result["compare_lib_differing_elements"] = int(
+            (back.view(bits) != back2.view(bits)).sum().item())
+        result["compare_lib_differing_wire_bytes"] = int(
+            (wire != wire2).sum().item())
     for name, (_fn, nbytes) in cases.items():
         ts = sorted(times[name])
         med = statistics.median(ts)
@@ -183,7 +236,7 @@ def main() -> None:
     x = torch.randn(m, generator=g)
     x[: m // 3] *= 1e-4
     x[-(m // 3):] *= 3e3
-    x = x.to(torch.bfloat16)
+    x = x.to(dtype)
     got = ops.mx8_pack(x.cuda()).cpu()
     want = mx8_pack_torch(x)
     result["payload_mismatch_fraction"] = (got[:m] != want[:m]).float().mean().item()

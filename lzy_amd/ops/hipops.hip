@@ -207,7 +207,9 @@ __device__ __forceinline__ uint32_t lz_mx8_scale_byte(uint32_t amax_bits) {
 // x * 2^(127-b), clamped to the e4m3 finite range, NaN kept.  The multiply
 // is exact (power of two) and finite values never exceed 448 by the choice
 // of b, so the explicit clamp only ever moves +-Inf.  med3 drops NaN, the
-// select puts it back as the one canonical quiet NaN (wire byte 0x7f).
+// select puts it back.  Which NaN reaches the convert is not relied on (a
+// negative NaN input has been seen to arrive with its sign): the one wire
+// byte of NaN, 0x7f, is made in lz_mx8_encode4, on the converted bytes.
 __device__ __forceinline__ float lz_mx8_scaled(float x, float mult) {
     const float v = x * mult;
     const float c = __builtin_amdgcn_fmed3f(v, -448.f, 448.f);
@@ -216,13 +218,20 @@ __device__ __forceinline__ float lz_mx8_scaled(float x, float mult) {
 
 // 4 floats -> 4 e4m3 bytes (byte k = element k), RNE: v_cvt_pk_fp8_f32, the
 // hardware convert behind __hip_fp8_e4m3 (OCP e4m3fn on gfx950), two
-// elements per instruction, written straight into the half-words of a dword
+// elements per instruction, written straight into the half-words of a dword.
+// A NaN can leave the convert as 0x7f or 0xff (a negative NaN input came
+// out as 0xff); the wire is deterministic and has one NaN byte, 0x7f, so the
+// sign bit of a NaN byte is cleared here.  A byte is NaN iff its low 7
+// bits are all ones: only then does adding 1 to them carry into bit 7 (and
+// never beyond the byte), which gives the sign bits to clear.
 __device__ __forceinline__ uint32_t lz_mx8_encode4(const float* f, float mult) {
     int w = __builtin_amdgcn_cvt_pk_fp8_f32(lz_mx8_scaled(f[0], mult),
                                             lz_mx8_scaled(f[1], mult), 0, false);
     w = __builtin_amdgcn_cvt_pk_fp8_f32(lz_mx8_scaled(f[2], mult),
                                         lz_mx8_scaled(f[3], mult), w, true);
-    return (uint32_t)w;
+    const uint32_t u = (uint32_t)w;
+    const uint32_t nan_sign = ((u & 0x7f7f7f7fu) + 0x01010101u) & 0x80808080u;
+    return u & ~nan_sign;
 }
 
 // a lane's 8 elements as fp32.  FULL: all 8 lie inside [0, n) and src + e0
@@ -382,11 +391,11 @@ __device__ __forceinline__ void lz_mx8_dec_load(const uint8_t* __restrict__ src,
 //
 // SIGNED_ZERO: for f16 the compiler folds the multiply and the convert into
 // one v_fma_mixlo_f16 (q * mult + 0), and -0 + 0 is +0: a negative-zero
-// payload byte, or a negative value that underflows f16, comes out +0.0
-// where the reference codec gives -0.0.  mx8_unpack_kernel keeps that
-// (equal as values; its callers compare values); the bundle decode is held
-// to the reference byte for byte and puts the sign back.
-template <typename T, bool ALIGNED, bool SIGNED_ZERO = false>
+// payload byte, or a negative value that underflows f16, would come out
+// +0.0 where the format says -0.0.  Decoded tensors are hashed as bytes
+// (device_checksum), so every decoder puts the sign back: two integer
+// operations per f16 element.
+template <typename T, bool ALIGNED, bool SIGNED_ZERO>
 __device__ __forceinline__ void lz_mx8_dec_store(const uint32_t (&w)[2], uint32_t b,
                                                  T* __restrict__ dst, int64_t g,
                                                  int64_t n) {
@@ -431,7 +440,7 @@ mx8_unpack_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst, int64_t 
         if (g * 8 >= n) continue;  // padded tail of the last block
         uint32_t w[2], b;
         lz_mx8_dec_load<ALIGNED>(src, scales, g, w, b);
-        lz_mx8_dec_store<T, ALIGNED>(w, b, dst, g, n);
+        lz_mx8_dec_store<T, ALIGNED, true>(w, b, dst, g, n);
     }
 }
 
@@ -1563,8 +1572,8 @@ extern "C" hipError_t lz_segcopy(const void* table_dev, int64_t nseg,
 // aligned and never straddle tiles.  A wired segment is therefore the bytes
 // lz_mx8_pack writes for the same leaf (same device functions, and a block's
 // bytes depend on the block's elements alone).  The decode is the body of
-// mx8_unpack_kernel with the sign of an f16 zero kept (lz_mx8_dec_store,
-// SIGNED_ZERO), which makes it byte-identical to the torch codec.
+// mx8_unpack_kernel (lz_mx8_dec_store, the sign of an f16 zero kept), so
+// both are byte-identical to the torch codec.
 //
 // Segment, mode and alignment class are functions of blockIdx and the table
 // only: wave-uniform.  Every wave of the workgroup walks its groups with a

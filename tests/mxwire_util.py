@@ -43,6 +43,46 @@ def assert_within_bound(got: torch.Tensor, x: torch.Tensor,
     return (err.norm() / w.norm().clamp_min(1e-300)).item()
 
 
+def assert_wire_equal(x_cpu: torch.Tensor, got: torch.Tensor,
+                      want: torch.Tensor, what: str = "") -> None:
+    """Two wire buffers of ``x_cpu`` byte for byte: scale bytes, payload and
+    the zero padding of the last block.  On a difference, reports the first
+    few elements with the input's bits, both codes and the scaled value
+    x * 2^(127-b) under the expected scale byte."""
+    n = x_cpu.numel()
+    nblk = (n + BLOCK - 1) // BLOCK
+    assert got.dtype == torch.uint8 and got.numel() == want.numel() == 33 * nblk, what
+    got, want = got.reshape(-1).cpu(), want.reshape(-1).cpu()
+    if torch.equal(got, want):
+        return
+    lines = []
+    sbad = (got[32 * nblk:] != want[32 * nblk:]).nonzero().reshape(-1)
+    for k in sbad[:8].tolist():
+        blk = x_cpu.reshape(-1)[32 * k: 32 * k + 32].float()
+        fin = blk[torch.isfinite(blk)].abs()
+        amax = fin.max() if fin.numel() else torch.zeros(())
+        lines.append(f"block {k}: scale byte got {got[32 * nblk + k].item()} "
+                     f"want {want[32 * nblk + k].item()}, amax bits "
+                     f"{amax.view(torch.int32).item() & 0xFFFFFFFF:#010x}")
+    pbad = (got[: 32 * nblk] != want[: 32 * nblk]).nonzero().reshape(-1)
+    flat = x_cpu.reshape(-1)
+    for i in pbad[:8].tolist():
+        if i >= n:
+            lines.append(f"padding byte {i}: got {got[i].item():#04x}, want 0x00")
+            continue
+        b = want[32 * nblk + i // BLOCK].item()
+        xi = flat[i: i + 1]
+        width = 8 * xi.element_size()
+        bits = xi.view(torch.int32 if width == 32 else torch.int16).item()
+        scaled = xi.double().item() * 2.0 ** (127 - b)
+        lines.append(f"element {i}: input bits {bits & ((1 << width) - 1):#x} "
+                     f"({xi.item()!r}), scale byte {b}, scaled {scaled!r}: "
+                     f"got {got[i].item():#04x} want {want[i].item():#04x}")
+    raise AssertionError(
+        f"{what}: {sbad.numel()} scale bytes and {pbad.numel()} payload bytes "
+        f"of {n} elements differ\n" + "\n".join(lines))
+
+
 def special_vector() -> torch.Tensor:
     """Four blocks: [zeros] [nan,1,0..] [inf,-inf,2,0..] [896,-1.75,3e38,1e-45,0..]."""
     v = torch.zeros(4 * BLOCK, dtype=torch.float32)

@@ -3,10 +3,10 @@ unpack_tensors_wire) on MI355X (gfx950), and a wired tensor bundle carried
 between two pool ranks on one GPU.
 
 Yardsticks, none of them the code under test: a wired segment is held byte
-for byte to the existing single-tensor kernel ``ops.mx8_pack`` and, with the
-hardware-rounding allowance of tests/test_gpu_mxwire.py, to the torch codec;
-raw segments, gaps and the whole decode direction are held byte for byte to
-the torch twins run on the CPU.  Host-side parts: tests/test_bundle_wire.py.
+for byte to the existing single-tensor kernel ``ops.mx8_pack`` and to the
+torch codec; raw segments, gaps and the whole decode direction are held
+byte for byte to the torch twins run on the CPU.  Host-side parts:
+tests/test_bundle_wire.py.
 """
 import os
 import random
@@ -22,7 +22,7 @@ import torch
 from lzy_amd import ops
 from lzy_amd.channels.mxwire import mx8_pack_torch, mx8_unpack_torch
 from lzy_amd.exceptions import NativeExtensionMissing
-from mxwire_util import check_special_decode, special_vector
+from mxwire_util import assert_wire_equal, check_special_decode, special_vector
 
 pytestmark = pytest.mark.gpu
 
@@ -109,24 +109,8 @@ def _capped(k):
 
 
 def _check_payload(x_cpu, got, want):
-    """A kernel-packed segment against the torch codec's: scale bytes exact,
-    payload within the allowance of tests/test_gpu_mxwire.py::_check_pack —
-    mismatch fraction <= 1e-3, each mismatch one adjacent code of one sign."""
-    n = x_cpu.numel()
-    nblk = (n + 31) // 32
-    assert got.numel() == want.numel() == 33 * nblk
-    assert torch.equal(got[32 * nblk:], want[32 * nblk:])
-    assert got[n: 32 * nblk].eq(0).all()  # padded payload of the last block
-    a = mx8_unpack_torch(got, n, torch.float32)
-    b = mx8_unpack_torch(want, n, torch.float32)
-    diff = a != b
-    mism = diff.float().mean().item()
-    assert mism <= 1e-3, f"payload mismatch fraction {mism} (n={n})"
-    if diff.any():
-        qa = got[:n][diff].to(torch.int32)
-        qb = want[:n][diff].to(torch.int32)
-        assert ((qa - qb).abs() == 1).all()
-        assert ((qa ^ qb) & 0x80).eq(0).all()
+    """A kernel-packed segment against the torch codec's, byte for byte."""
+    assert_wire_equal(x_cpu, got, want, f"wired segment n={x_cpu.numel()}")
 
 
 def _check_encoded(leaves, wired, got, want, offs):
