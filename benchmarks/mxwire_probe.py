@@ -1,5 +1,7 @@
-"""Byte-rate probe for the block-scaled FP8 (mxfp8) wire kernels (run on
-an MI355X).
+"""Byte-rate probe for the block-scaled 8-bit wire kernels (run on an
+MI355X).  ``--codec mxint8`` times the ``mxi8_*`` kernels in place of the
+``mx8_*`` ones named below; ``--compare-lib`` always adds the other build's
+``lz_mx8_*``, which move the same bytes.
 
 On a 1 GiB bf16 buffer (``--dtype f16`` / ``f32``: as many bytes of that
 type), times in one process, interleaved round-robin:
@@ -41,7 +43,7 @@ sys.path.insert(0, __file__.rsplit("/", 2)[0])
 import torch
 
 import lzy_amd.ops as ops
-from lzy_amd.channels.mxwire import mx8_pack_torch
+from lzy_amd.channels import mxwire
 
 
 def _time_alternating(cases, iters, warmup):
@@ -70,9 +72,12 @@ def axpby_mode(args) -> None:
     wire = torch.empty(ops.mx8_nbytes(n), device="cuda", dtype=torch.uint8)
     src = torch.empty(n, device="cuda", dtype=torch.bfloat16)
     ops.fill_pattern(src, seed=3, mask16=0x3FFF)  # finite positive bf16
-    ops.mx8_pack(src, out=wire)
+    pre = _PREFIX[args.codec]
+    pack, unpack, axpby = (getattr(ops, f"{pre}_{k}") for k in ("pack", "unpack", "axpby"))
+    pack(src, out=wire)
     del src
-    result = {"mode": "axpby", "melems": args.melems, "iters": args.iters}
+    result = {"mode": "axpby", "codec": args.codec, "melems": args.melems,
+              "iters": args.iters}
     for dtype, name in ((torch.bfloat16, "bf16"), (torch.float32, "f32")):
         es = 2 if dtype == torch.bfloat16 else 4
         torch.manual_seed(5)
@@ -82,10 +87,10 @@ def axpby_mode(args) -> None:
         tmp = torch.empty_like(a)
 
         def fused():
-            ops.mx8_axpby(a, wire, alpha, beta, dst=out_f)
+            axpby(a, wire, alpha, beta, dst=out_f)
 
         def sequence():
-            ops.mx8_unpack(wire, n, dtype, out=tmp)
+            unpack(wire, n, dtype, out=tmp)
             ops.axpby(a, tmp, alpha, beta, dst=out_s)
 
         ts = _time_alternating({"fused": fused, "sequence": sequence},
@@ -124,11 +129,13 @@ def axpby_mode(args) -> None:
 
 
 _DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
+_PREFIX = {"mxfp8": "mx8", "mxint8": "mxi8"}
 
 
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["codec", "axpby"], default="codec")
+    ap.add_argument("--codec", choices=sorted(_PREFIX), default="mxfp8")
     ap.add_argument("--melems", type=int, default=64,
                     help="axpby mode: Mi elements per buffer")
     ap.add_argument("--mib", type=int, default=1024, help="tensor buffer size")
@@ -155,13 +162,15 @@ def main() -> None:
     wire = torch.empty(ops.mx8_nbytes(n), device="cuda", dtype=torch.uint8)
     fp8 = torch.empty(n, device="cuda", dtype=torch.float8_e4m3fn)
     back = torch.empty(n, device="cuda", dtype=dtype)
-    ops.mx8_pack(src, out=wire)
+    pre = _PREFIX[args.codec]
+    pack, unpack = getattr(ops, f"{pre}_pack"), getattr(ops, f"{pre}_unpack")
+    pack(src, out=wire)
     ops.cast_copy(src, fp8)
 
     cases = {
-        "mx8_pack": (lambda: ops.mx8_pack(src, out=wire), es * n + wire.numel()),
-        "mx8_unpack": (lambda: ops.mx8_unpack(wire, n, dtype, out=back),
-                       wire.numel() + es * n),
+        f"{pre}_pack": (lambda: pack(src, out=wire), es * n + wire.numel()),
+        f"{pre}_unpack": (lambda: unpack(wire, n, dtype, out=back),
+                          wire.numel() + es * n),
         f"cast_{dname}_to_e4m3": (lambda: ops.cast_copy(src, fp8), es * n + n),
         f"cast_e4m3_to_{dname}": (lambda: ops.cast_copy(fp8, back), n + es * n),
     }
@@ -177,6 +186,7 @@ def main() -> None:
                                       ctypes.c_void_p]
         back2 = torch.empty_like(back)
         wire2 = torch.empty_like(wire)
+        ops.mx8_pack(src, out=wire2)  # what the other build's unpack reads
         code = ops._dtype_code(dtype)
 
         def other_pack():
@@ -185,7 +195,7 @@ def main() -> None:
             assert err == 0, err
 
         def other_unpack():
-            err = other.lz_mx8_unpack(wire.data_ptr(), back2.data_ptr(), code, n,
+            err = other.lz_mx8_unpack(wire2.data_ptr(), back2.data_ptr(), code, n,
                                       ops._current_stream_ptr())
             assert err == 0, err
 
@@ -207,8 +217,9 @@ def main() -> None:
             e1.synchronize()
             times[name].append(e0.elapsed_time(e1) * 1e-3)
 
-    result = {"buffer_mib": args.mib, "dtype": dname, "iters": args.iters}
-    if args.compare_lib:
+    result = {"buffer_mib": args.mib, "dtype": dname, "iters": args.iters,
+              "codec": args.codec}
+    if args.compare_lib and args.codec == "mxfp8":
         ops.mx8_unpack(wire, n, dtype, out=back)
         other_unpack()
         torch.cuda.synchronize()
@@ -237,8 +248,8 @@ def main() -> None:
     x[: m // 3] *= 1e-4
     x[-(m // 3):] *= 3e3
     x = x.to(dtype)
-    got = ops.mx8_pack(x.cuda()).cpu()
-    want = mx8_pack_torch(x)
+    got = pack(x.cuda()).cpu()
+    want = getattr(mxwire, f"{pre}_pack_torch")(x)
     result["payload_mismatch_fraction"] = (got[:m] != want[:m]).float().mean().item()
     result["scale_mismatches"] = int((got[m:] != want[m:]).sum().item())
     print(f"payload mismatch fraction vs torch codec: "

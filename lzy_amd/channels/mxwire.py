@@ -1,4 +1,5 @@
-"""Block-scaled FP8 wire codec (OCP MXFP8; format spec: docs/mxwire.md).
+"""Block-scaled 8-bit wire codecs (OCP MXFP8 and MXINT8; format spec:
+docs/mxwire.md).
 
 Every 32 consecutive elements share one power-of-two scale byte (E8M0)
 and travel as one OCP ``e4m3fn`` byte each.  For ``numel`` elements,
@@ -16,10 +17,16 @@ and are the kernels' test oracle.  ``mx8_pack``/``mx8_unpack`` dispatch.
 ``mx8_axpby_torch`` is the reference of the fused decode-combine
 (``lzy_amd.ops.mx8_axpby``), the combine of a wire-cast merge-tree edge
 (channels/treeplan.py); ``mx8_axpby`` dispatches the same way.
+
+The ``mxi8_*`` functions are the same three layers for MXINT8: same buffer,
+same scale byte position, int8 elements (``q * 2^(b-133)``, ``0x80`` is
+NaN) — about a third of the error on tensors whose blocks have a narrow
+dynamic range.  ``wire_codec(name)`` maps a wire name (``"mxfp8"``,
+``"mxint8"``) to its dispatching ``(pack, unpack, axpby)``.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Union
+from typing import Callable, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -38,24 +45,30 @@ def _numel(shape: Sequence[int]) -> int:
     return n
 
 
-def mx8_pack_torch(t: torch.Tensor) -> torch.Tensor:
-    """Encode ``t`` (f32/bf16/f16, any device) with torch ops only."""
+def _blocks(t: torch.Tensor, op: str):
+    """``t`` as fp32 blocks ``[nblk, 32]`` (the padded tail is 0.0), the raw
+    bits of each block's amax over its finite elements (for |x| the integer
+    order is the float order), and the empty wire buffer."""
     if t.dtype not in _MX_DTYPES:
-        raise ValueError(f"mx8_pack: dtype must be f32/bf16/f16, got {t.dtype}")
+        raise ValueError(f"{op}: dtype must be f32/bf16/f16, got {t.dtype}")
     x = t.detach().reshape(-1).to(torch.float32)
     n = x.numel()
     nblk = (n + MX_BLOCK - 1) // MX_BLOCK
     out = torch.empty(33 * nblk, dtype=torch.uint8, device=x.device)
-    if n == 0:
-        return out
-    if nblk * MX_BLOCK != n:  # the padded tail encodes as 0.0
+    if nblk * MX_BLOCK != n:
         x = torch.cat([x, x.new_zeros(nblk * MX_BLOCK - n)])
     x = x.view(nblk, MX_BLOCK)
-    # amax over the block's finite elements, on raw bits (for |x| the
-    # integer order is the float order)
     mag = x.view(torch.int32) & 0x7FFFFFFF
     mag = torch.where(mag < 0x7F800000, mag, torch.zeros_like(mag))
-    amax = mag.amax(dim=1)
+    return x, mag.amax(dim=1) if n else mag.new_zeros(0), out
+
+
+def mx8_pack_torch(t: torch.Tensor) -> torch.Tensor:
+    """Encode ``t`` (f32/bf16/f16, any device) with torch ops only."""
+    x, amax, out = _blocks(t, "mx8_pack")
+    nblk = x.shape[0]
+    if nblk == 0:
+        return out
     e = amax >> 23
     m = amax & 0x7FFFFF
     # smallest 2^(b-127) with amax / 2^(b-127) <= 448 = 1.75 * 2^8
@@ -93,6 +106,59 @@ def mx8_unpack_torch(buf: torch.Tensor, shape: Union[int, Sequence[int]],
     return x.reshape(-1)[:n].to(dtype).reshape(shape)
 
 
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """fp32 ``2^e`` from int32 ``e`` in [-149, 127], subnormals included."""
+    bits = torch.where(e >= -126, (e + 127) << 23,
+                       torch.ones_like(e) << (e + 149).clamp(0, 22))
+    return bits.to(torch.int32).view(torch.float32)
+
+
+def mxi8_pack_torch(t: torch.Tensor) -> torch.Tensor:
+    """Encode ``t`` (f32/bf16/f16, any device) as MXINT8 with torch ops only."""
+    x, amax, out = _blocks(t, "mxi8_pack")
+    nblk = x.shape[0]
+    if nblk == 0:
+        return out
+    # smallest b with rne(amax * 2^(133-b)) <= 127: b = E, one more from
+    # m = 0x7f0000 on (a subnormal amax: b = 0, one more from 0x7f8000 on)
+    b = ((amax + torch.where(amax < 0x00800000, 0x8000, 0x10000)) >> 23).clamp_(max=254)
+    # x * 2^(133-b) is exact, but 2^(133-b) is no fp32 for b < 6: two exact
+    # multiplies by 2^h and 2^(e-h).  Where the first loses bits to the
+    # subnormal range (e < 0 only) the result rounds to zero either way.
+    e = 133 - b
+    h = e >> 1
+    v = (x * _pow2(h)[:, None]) * _pow2(e - h)[:, None]
+    v = torch.clamp(v, -127.0, 127.0)  # +-Inf, and the b == 254 cap; NaN stays
+    q = torch.where(torch.isnan(v), torch.full_like(v, -128.0), torch.round(v))
+    out[: 32 * nblk] = q.to(torch.int8).view(torch.uint8).reshape(-1)
+    out[32 * nblk:] = b.to(torch.uint8)
+    return out
+
+
+def mxi8_unpack_torch(buf: torch.Tensor, shape: Union[int, Sequence[int]],
+                      dtype: torch.dtype) -> torch.Tensor:
+    """Decode an MXINT8 wire buffer into a tensor of ``shape``/``dtype``."""
+    if dtype not in _MX_DTYPES:
+        raise ValueError(f"mxi8_unpack: dtype must be f32/bf16/f16, got {dtype}")
+    shape = (int(shape),) if isinstance(shape, int) else tuple(shape)
+    n = _numel(shape)
+    nblk = (n + MX_BLOCK - 1) // MX_BLOCK
+    if buf.dtype != torch.uint8 or buf.numel() != 33 * nblk:
+        raise ValueError(
+            f"mxi8_unpack: buffer must be uint8[{33 * nblk}] for {n} elements, "
+            f"got {buf.dtype}[{buf.numel()}]"
+        )
+    if n == 0:
+        return torch.empty(shape, dtype=dtype, device=buf.device)
+    buf = buf.reshape(-1)
+    q = buf[: 32 * nblk].contiguous().view(torch.int8).view(nblk, MX_BLOCK)
+    b = buf[32 * nblk:].to(torch.int32)
+    # q * 2^(b-133): exact in fp32 for every b (2^-133 is a subnormal)
+    x = q.to(torch.float32) * _pow2(b - 133)[:, None]
+    x = torch.where(q == -128, torch.full_like(x, float("nan")), x)
+    return x.reshape(-1)[:n].to(dtype).reshape(shape)
+
+
 def _f32(v: float) -> float:
     # the kernel takes alpha/beta as C floats
     return float(torch.tensor(float(v), dtype=torch.float32))
@@ -110,14 +176,27 @@ def mx8_axpby_torch(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
     (default: ``a.dtype``).  The kernel's FMA rounds the exact sum once, so
     the two differ by at most the float64 rounding ahead of the fp32 one.
     """
+    return _axpby_torch("mx8_axpby", mx8_unpack_torch, a, wire, alpha, beta,
+                        out_dtype)
+
+
+def mxi8_axpby_torch(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
+                     beta: float = 1.0,
+                     out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """:func:`mx8_axpby_torch` for an MXINT8 ``wire``."""
+    return _axpby_torch("mxi8_axpby", mxi8_unpack_torch, a, wire, alpha, beta,
+                        out_dtype)
+
+
+def _axpby_torch(op, unpack_torch, a, wire, alpha, beta, out_dtype):
     if a.dtype not in _MX_DTYPES:
-        raise ValueError(f"mx8_axpby: dtype must be f32/bf16/f16, got {a.dtype}")
+        raise ValueError(f"{op}: dtype must be f32/bf16/f16, got {a.dtype}")
     out_dtype = a.dtype if out_dtype is None else out_dtype
     if out_dtype not in _MX_DTYPES:
         raise ValueError(
-            f"mx8_axpby: out dtype must be f32/bf16/f16, got {out_dtype}"
+            f"{op}: out dtype must be f32/bf16/f16, got {out_dtype}"
         )
-    x = mx8_unpack_torch(wire, a.numel(), torch.float32)  # checks the buffer
+    x = unpack_torch(wire, a.numel(), torch.float32)  # checks the buffer
     p = x * torch.tensor(_f32(beta), dtype=torch.float32, device=x.device)
     af = a.detach().reshape(-1).to(torch.float64)
     r = (af * _f32(alpha) + p.to(torch.float64)).to(torch.float32)
@@ -135,21 +214,45 @@ def _native(t: torch.Tensor) -> bool:
     return ops.NATIVE
 
 
-def mx8_pack(t: torch.Tensor) -> torch.Tensor:
+def _pack(op: str, pack_torch: Callable, t: torch.Tensor) -> torch.Tensor:
     if _native(t):
         from lzy_amd import ops
 
-        return ops.mx8_pack(t)
-    return mx8_pack_torch(t)
+        return getattr(ops, op)(t)
+    return pack_torch(t)
+
+
+def _unpack(op: str, unpack_torch: Callable, buf, shape, dtype) -> torch.Tensor:
+    if _native(buf):
+        from lzy_amd import ops
+
+        return getattr(ops, op)(buf, shape, dtype)
+    return unpack_torch(buf, shape, dtype)
+
+
+def _axpby(op: str, axpby_torch: Callable, a, wire, alpha, beta, dst):
+    if _native(a):
+        from lzy_amd import ops
+
+        return getattr(ops, op)(a, wire, alpha, beta, dst=dst)
+    if dst is None:
+        return axpby_torch(a, wire, alpha, beta)
+    if dst.shape != a.shape:
+        raise ValueError(
+            f"{op}: dst has shape {tuple(dst.shape)}, "
+            f"expected {tuple(a.shape)}"
+        )
+    dst.copy_(axpby_torch(a, wire, alpha, beta, out_dtype=dst.dtype))
+    return dst
+
+
+def mx8_pack(t: torch.Tensor) -> torch.Tensor:
+    return _pack("mx8_pack", mx8_pack_torch, t)
 
 
 def mx8_unpack(buf: torch.Tensor, shape: Union[int, Sequence[int]],
                dtype: torch.dtype) -> torch.Tensor:
-    if _native(buf):
-        from lzy_amd import ops
-
-        return ops.mx8_unpack(buf, shape, dtype)
-    return mx8_unpack_torch(buf, shape, dtype)
+    return _unpack("mx8_unpack", mx8_unpack_torch, buf, shape, dtype)
 
 
 def mx8_axpby(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
@@ -157,16 +260,35 @@ def mx8_axpby(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
               dst: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``dst = alpha*a + beta*decode(wire)``; returns ``dst`` (a new tensor
     like ``a`` when not given; ``dst`` may be ``a``)."""
-    if _native(a):
-        from lzy_amd import ops
+    return _axpby("mx8_axpby", mx8_axpby_torch, a, wire, alpha, beta, dst)
 
-        return ops.mx8_axpby(a, wire, alpha, beta, dst=dst)
-    if dst is None:
-        return mx8_axpby_torch(a, wire, alpha, beta)
-    if dst.shape != a.shape:
-        raise ValueError(
-            f"mx8_axpby: dst has shape {tuple(dst.shape)}, "
-            f"expected {tuple(a.shape)}"
-        )
-    dst.copy_(mx8_axpby_torch(a, wire, alpha, beta, out_dtype=dst.dtype))
-    return dst
+
+def mxi8_pack(t: torch.Tensor) -> torch.Tensor:
+    return _pack("mxi8_pack", mxi8_pack_torch, t)
+
+
+def mxi8_unpack(buf: torch.Tensor, shape: Union[int, Sequence[int]],
+                dtype: torch.dtype) -> torch.Tensor:
+    return _unpack("mxi8_unpack", mxi8_unpack_torch, buf, shape, dtype)
+
+
+def mxi8_axpby(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
+               beta: float = 1.0,
+               dst: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`mx8_axpby` for an MXINT8 ``wire``."""
+    return _axpby("mxi8_axpby", mxi8_axpby_torch, a, wire, alpha, beta, dst)
+
+
+# wire name (channel_wire_cast, stream_wire_cast, a plan's "wire") -> the
+# dispatching (pack, unpack, axpby); both codecs share mx8_nbytes
+_WIRE_CODECS = {
+    "mxfp8": (mx8_pack, mx8_unpack, mx8_axpby),
+    "mxint8": (mxi8_pack, mxi8_unpack, mxi8_axpby),
+}
+MX_WIRES = tuple(_WIRE_CODECS)
+
+
+def wire_codec(wire: str) -> Tuple[Callable, Callable, Callable]:
+    if wire not in _WIRE_CODECS:
+        raise ValueError(f"wire must be one of {MX_WIRES}, got {wire!r}")
+    return _WIRE_CODECS[wire]

@@ -37,19 +37,23 @@ def streamed_reduce_pair(
     its ``t`` in chunks and returns None.  Both sides must pass the same
     shape/dtype/chunk_bytes and the same ``wire``.
 
-    ``wire="mxfp8"`` (f32/bf16/f16 only): chunks are a multiple of 256
-    elements and cross the link as self-contained MXFP8 buffers
-    (docs/mxwire.md); the sender packs each one, the receiver combines
-    with the fused decode ``mx8_axpby``.
+    ``wire="mxfp8"`` or ``"mxint8"`` (f32/bf16/f16 only): chunks are a
+    multiple of 256 elements and cross the link as self-contained buffers
+    of that codec (docs/mxwire.md); the sender packs each one, the receiver
+    combines with the codec's fused decode (``mx8_axpby``, ``mxi8_axpby``).
+    Device tensors on a gloo group are staged through the host as packed
+    bytes: packed by the kernel before, combined by the kernel after.
     """
-    if wire not in ("", "mxfp8"):
+    from lzy_amd.channels import mxwire
+
+    if wire not in ("",) + mxwire.MX_WIRES:
         raise ValueError(f"streamed_reduce_pair: unknown wire {wire!r}")
     flat = t.detach().contiguous().view(-1)
     n = flat.numel()
     per = max(1, chunk_bytes // max(1, flat.element_size()))
     if wire:
         return _streamed_reduce_pair_mx(
-            t, flat, peer, is_receiver, alpha, beta, per, group
+            t, flat, peer, is_receiver, alpha, beta, per, group, wire
         )
     starts = list(range(0, n, per))
 
@@ -98,21 +102,27 @@ def streamed_reduce_pair(
     return out.view(t.shape)
 
 
-def _streamed_reduce_pair_mx(t, flat, peer, is_receiver, alpha, beta, per, group):
+def _streamed_reduce_pair_mx(t, flat, peer, is_receiver, alpha, beta, per, group,
+                             wire):
     from lzy_amd.channels import mxwire
 
     if flat.dtype not in (torch.float32, torch.float16, torch.bfloat16):
         raise ValueError(
-            f"streamed_reduce_pair: wire=mxfp8 needs f32/bf16/f16, "
+            f"streamed_reduce_pair: wire={wire} needs f32/bf16/f16, "
             f"got {flat.dtype}"
         )
+    pack, _, axpby = mxwire.wire_codec(wire)
     n = flat.numel()
     per = -(-per // 256) * 256  # whole blocks, 16 B-aligned chunk starts
     starts = list(range(0, n, per))
+    # gloo carries host memory: only the packed bytes cross PCIe
+    host_stage = flat.is_cuda and dist.get_backend(group) == "gloo"
 
     if not is_receiver:
         # packed chunks stay alive until their sends are waited on
-        packed = [mxwire.mx8_pack(flat[s: min(s + per, n)]) for s in starts]
+        packed = [pack(flat[s: min(s + per, n)]) for s in starts]
+        if host_stage:
+            packed = [p.cpu() for p in packed]
         works = [dist.isend(p, dst=peer, group=group) for p in packed]
         for w in works:
             w.wait()
@@ -121,7 +131,8 @@ def _streamed_reduce_pair_mx(t, flat, peer, is_receiver, alpha, beta, per, group
     out = torch.empty_like(flat)
     bufs = [
         torch.empty(mxwire.mx8_nbytes(min(per, n)), dtype=torch.uint8,
-                    device=flat.device)
+                    device=None if host_stage else flat.device,
+                    pin_memory=host_stage)
         for _ in range(2)
     ]
 
@@ -136,6 +147,8 @@ def _streamed_reduce_pair_mx(t, flat, peer, is_receiver, alpha, beta, per, group
         w, s, ln, wb = inflight
         nxt = post(i + 1) if i + 1 < len(starts) else None
         w.wait()
-        mxwire.mx8_axpby(flat[s: s + ln], wb, alpha, beta, dst=out[s: s + ln])
+        if host_stage:
+            wb = wb.to(flat.device)
+        axpby(flat[s: s + ln], wb, alpha, beta, dst=out[s: s + ln])
         inflight = nxt
     return out.view(t.shape)

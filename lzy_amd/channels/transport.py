@@ -212,20 +212,23 @@ def _should_wirecast(dtype: torch.dtype, numel: int, wire) -> bool:
     )
 
 
-# "mxfp8" is not a torch dtype: block-scaled FP8 (channels/mxwire.py) packs
-# into a flat uint8 buffer, which every path carries — RCCL device, the
-# host-staged fallback and CPU tensors over gloo.
-_MX_WIRE = "mxfp8"
+# "mxfp8" and "mxint8" are not torch dtypes: the block-scaled 8-bit codecs
+# (channels/mxwire.py) pack into a flat uint8 buffer, which every path
+# carries — RCCL device, the host-staged fallback and CPU tensors over gloo.
 
 
-def wire_cast_mx() -> bool:
+def wire_cast_mx() -> str:
+    """The block-scaled codec ``channel_wire_cast`` names ("mxfp8",
+    "mxint8"), or "" when it names none."""
+    from lzy_amd.channels.mxwire import MX_WIRES
     from lzy_amd.config import get_config
 
-    return get_config().channel_wire_cast == _MX_WIRE
+    wire = get_config().channel_wire_cast
+    return wire if wire in MX_WIRES else ""
 
 
-def _should_mxcast(dtype: torch.dtype, numel: int, enabled: bool) -> bool:
-    return enabled and dtype in _WIRE_CASTABLE and numel >= _WIRE_MIN_ELEMS
+def _should_mxcast(dtype: torch.dtype, numel: int, enabled) -> bool:
+    return bool(enabled) and dtype in _WIRE_CASTABLE and numel >= _WIRE_MIN_ELEMS
 
 
 def _pack_contiguous(t: torch.Tensor) -> torch.Tensor:
@@ -388,12 +391,12 @@ class Transport:
             # sides derive it from (producer device, _cuda_p2p, config).
             # fp8 wire dtypes are RCCL-device-path only — gloo (CPU
             # tensors, host-staged fallback) cannot carry float8.
-            # mxfp8 packs to flat uint8 BEFORE host staging (a host-staged
-            # device tensor is packed by the kernel) and rides every path.
+            # mxfp8/mxint8 pack to flat uint8 BEFORE host staging (a host-
+            # staged device tensor is packed by the kernel), ride every path.
             if _should_mxcast(t.dtype, t.numel(), self._mx):
                 from lzy_amd.channels import mxwire
 
-                t = mxwire.mx8_pack(t)
+                t = mxwire.wire_codec(self._mx)[0](t)
             elif self._wire_allowed(t.is_cuda) and _should_wirecast(
                 t.dtype, t.numel(), self._wire
             ):
@@ -510,7 +513,7 @@ class Transport:
                 if want_cuda and not on_device:
                     out = out.to(self._device, non_blocking=False)
                 if mx:
-                    out = mxwire.mx8_unpack(out, meta.shape, dtype)
+                    out = mxwire.wire_codec(self._mx)[1](out, meta.shape, dtype)
                 elif casted:
                     out = wire_unpack(out, dtype)
                 return out

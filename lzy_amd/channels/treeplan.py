@@ -29,12 +29,13 @@ the driver keeps at most one plan active pool-wide, and per (src, dst)
 pair every rank issues chunk-major in global topo order — pairwise
 consistent by construction (checked at build time).
 
-Wire format: with ``build_plan(..., wire="mxfp8")`` (driver config
-``stream_wire_cast``) the remote edges of an f32/bf16/f16 plan cross the
-link as block-scaled FP8 chunks — each chunk a self-contained MXFP8
-buffer, packed by the sender and combined by the fused decode
-``mxwire.mx8_axpby`` on arrival (docs/mxwire.md, "Plans").  The decision
-travels in the plan; ranks never consult their own configuration.
+Wire format: with ``build_plan(..., wire="mxfp8")`` or ``"mxint8"`` (driver
+config ``stream_wire_cast``) the remote edges of an f32/bf16/f16 plan cross
+the link as block-scaled 8-bit chunks — each chunk a self-contained MXFP8
+or MXINT8 buffer, packed by the sender and combined by the codec's fused
+decode (``mxwire.mx8_axpby``, ``mxwire.mxi8_axpby``) on arrival
+(docs/mxwire.md, "Plans").  The decision travels in the plan; ranks never
+consult their own configuration.
 """
 from __future__ import annotations
 
@@ -50,7 +51,7 @@ from lzy_amd.utils.metrics import METRICS
 
 _LOG = logging.getLogger("lzy_amd.treeplan")
 
-WIRE_MODES = ("", "mxfp8")
+WIRE_MODES = ("", "mxfp8", "mxint8")
 _WIRE_DTYPES = ("float32", "bfloat16", "float16")
 WIRE_MIN_NUMEL = 65536      # the transport's wire-cast threshold
 WIRE_CHUNK_QUANTUM = 256    # elements; chunk_elems of a wired plan
@@ -154,8 +155,8 @@ def build_plan(
     order inconsistency) — the caller then falls back to op-by-op
     execution.
 
-    ``wire="mxfp8"`` asks for the block-scaled FP8 wire (docs/mxwire.md) on
-    the plan's remote edges.  The driver alone decides: the plan carries
+    ``wire="mxfp8"`` / ``"mxint8"`` asks for that block-scaled 8-bit wire
+    (docs/mxwire.md) on the plan's remote edges.  The driver alone decides: the plan carries
     the outcome in ``plan["wire"]`` and ranks follow it, never their own
     configuration.  Plans of another dtype or under the transport's size
     threshold stay exact (``"wire": ""``).
@@ -284,7 +285,7 @@ def build_plan(
     if numel // per < 4:
         per = max((1 << 20) // elem, math.ceil(numel / 4))
     wired = (
-        wire == "mxfp8" and dtype in _WIRE_DTYPES and numel >= WIRE_MIN_NUMEL
+        wire != "" and dtype in _WIRE_DTYPES and numel >= WIRE_MIN_NUMEL
     )
     if wired:
         # whole blocks per chunk: every chunk but the last is a multiple of
@@ -301,7 +302,7 @@ def build_plan(
         "dtype": dtype,
         "numel": numel,
         "chunk_elems": per,
-        "wire": "mxfp8" if wired else "",
+        "wire": wire if wired else "",
         "device_cuda": device_cuda,
         "cuda_p2p": bool(cuda_p2p),
         "steps_by_rank": steps_by_rank,
@@ -343,11 +344,13 @@ def run_stream_plan(
     on_device = want_cuda and cuda_p2p
     host_stage = want_cuda and not cuda_p2p  # oversubscribed harnesses
     # wired plan (docs/mxwire.md, "Plans"): every chunk crosses the link as
-    # a self-contained MXFP8 buffer.  A plan dict without the key is unwired.
-    wired = plan.get("wire", "") == "mxfp8"
+    # a self-contained buffer of the plan's codec.  A plan dict without the
+    # key is unwired.
+    wired = plan.get("wire", "") != ""
     if wired:
         from lzy_amd.channels import mxwire
 
+        wire_pack, _, wire_axpby = mxwire.wire_codec(plan["wire"])
         wper = mxwire.mx8_nbytes(per)  # chunk j starts at byte j * wper
 
     def flat_entry(eid: str) -> torch.Tensor:
@@ -471,7 +474,7 @@ def run_stream_plan(
             if wired:
                 # pack where the chunk lives (the kernel, for a device
                 # chunk), THEN stage: only packed bytes cross PCIe
-                t = mxwire.mx8_pack(t)
+                t = wire_pack(t)
                 staged.append(t)
             stats["wire_bytes"] += t.numel() * t.element_size()
             if host_stage and t.is_cuda:
@@ -528,8 +531,8 @@ def run_stream_plan(
                     if wired:
                         # decode fused into the combine: no plan-dtype
                         # temporary of the received chunk
-                        mxwire.mx8_axpby(a[s:e], b_c, st["alpha"], st["beta"],
-                                         dst=out[s:e])
+                        wire_axpby(a[s:e], b_c, st["alpha"], st["beta"],
+                                   dst=out[s:e])
                     else:
                         combine(out[s:e], a[s:e], b_c, st["alpha"], st["beta"])
                 else:

@@ -23,6 +23,7 @@ _lib: Optional[ctypes.CDLL] = None
 _load_error: Optional[str] = None
 _MX8 = False  # libhipops.so exports lz_mx8_pack / lz_mx8_unpack
 _MX8_AXPBY = False  # ... and lz_mx8_axpby (the fused decode-combine)
+_MXI8 = False  # ... and lz_mxi8_pack / lz_mxi8_unpack / lz_mxi8_axpby (MXINT8)
 _SEGCOPY = False  # ... and lz_segcopy (the packed-bundle gather/scatter)
 # bytes per tile of the segmented copy — LZ_SEG_TILE in hipops.hip
 SEGCOPY_TILE = 16384
@@ -142,6 +143,27 @@ def _try_load() -> Optional[ctypes.CDLL]:
         _MX8_AXPBY = True
     except AttributeError:
         _MX8_AXPBY = False
+    global _MXI8
+    try:
+        lib.lz_mxi8_pack.restype = ctypes.c_int
+        lib.lz_mxi8_pack.argtypes = [
+            ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+            ctypes.c_void_p,
+        ]
+        lib.lz_mxi8_unpack.restype = ctypes.c_int
+        lib.lz_mxi8_unpack.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+            ctypes.c_void_p,
+        ]
+        lib.lz_mxi8_axpby.restype = ctypes.c_int
+        lib.lz_mxi8_axpby.argtypes = [
+            ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
+            ctypes.c_void_p,
+        ]
+        _MXI8 = True
+    except AttributeError:
+        _MXI8 = False
     global _SEGCOPY
     try:
         lib.lz_segcopy.restype = ctypes.c_int
@@ -281,9 +303,24 @@ def _require_mx8() -> ctypes.CDLL:
     return lib
 
 
+def _mx_entry(op: str):
+    """The C entry point ``lz_<op>`` of an ``mx8_*`` / ``mxi8_*`` wrapper; a
+    library built before it raises, whatever else it can still do."""
+    if op.startswith("mx8_") and op != "mx8_axpby":
+        return getattr(_require_mx8(), "lz_" + op)
+    lib = _require_native()
+    if not (_MX8_AXPBY if op == "mx8_axpby" else _MXI8):
+        raise NativeExtensionMissing(
+            f"{_LIB_PATH} is stale: it lacks lz_{op}; "
+            f"rebuild with `python setup.py build_ext --inplace --force`"
+        )
+    return getattr(lib, "lz_" + op)
+
+
 def mx8_nbytes(numel: int) -> int:
-    """Wire bytes of ``numel`` elements in the block-scaled FP8 format:
-    32 e4m3 payload bytes + 1 scale byte per 32-element block."""
+    """Wire bytes of ``numel`` elements in the block-scaled 8-bit formats
+    (MXFP8 and MXINT8 alike): 32 payload bytes + 1 scale byte per
+    32-element block."""
     return 33 * ((int(numel) + 31) // 32)
 
 
@@ -299,12 +336,22 @@ def mx8_pack(t, out=None):
     wire format (docs/mxwire.md): one fused amax-reduce + scale + e4m3
     quantize pass on the current stream.  Returns a flat uint8 tensor of
     ``mx8_nbytes(t.numel())`` bytes (``out`` when given)."""
+    return _mx_pack("mx8_pack", t, out)
+
+
+def mxi8_pack(t, out=None):
+    """:func:`mx8_pack` for the block-scaled INT8 (MXINT8) wire format
+    (docs/mxwire.md): same buffer size and layout, int8 elements."""
+    return _mx_pack("mxi8_pack", t, out)
+
+
+def _mx_pack(op: str, t, out):
     import torch
 
     if not t.is_cuda:
-        raise ValueError("mx8_pack requires a device tensor")
-    _mx8_check_dtype(t.dtype, "mx8_pack")
-    lib = _require_mx8()
+        raise ValueError(f"{op} requires a device tensor")
+    _mx8_check_dtype(t.dtype, op)
+    fn = _mx_entry(op)
     s = t.detach().contiguous()
     n = s.numel()
     nbytes = mx8_nbytes(n)
@@ -313,10 +360,10 @@ def mx8_pack(t, out=None):
     elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
               and out.numel() == nbytes):
         raise ValueError(
-            f"mx8_pack: out must be a contiguous device uint8[{nbytes}]"
+            f"{op}: out must be a contiguous device uint8[{nbytes}]"
         )
     _check(
-        lib.lz_mx8_pack(
+        fn(
             ctypes.c_void_p(s.data_ptr()),
             _dtype_code(s.dtype),
             ctypes.c_void_p(out.data_ptr()),
@@ -330,6 +377,15 @@ def mx8_pack(t, out=None):
 def mx8_unpack(buf, numel_or_shape, dtype, out=None):
     """Decode an MXFP8 wire buffer (device uint8) into a tensor of
     ``dtype`` (f32/bf16/f16) and the given numel or shape."""
+    return _mx_unpack("mx8_unpack", buf, numel_or_shape, dtype, out)
+
+
+def mxi8_unpack(buf, numel_or_shape, dtype, out=None):
+    """:func:`mx8_unpack` for an MXINT8 wire buffer."""
+    return _mx_unpack("mxi8_unpack", buf, numel_or_shape, dtype, out)
+
+
+def _mx_unpack(op: str, buf, numel_or_shape, dtype, out):
     import torch
 
     if isinstance(numel_or_shape, int):
@@ -340,24 +396,24 @@ def mx8_unpack(buf, numel_or_shape, dtype, out=None):
     for d in shape:
         n *= d
     if not buf.is_cuda:
-        raise ValueError("mx8_unpack requires a device buffer")
-    _mx8_check_dtype(dtype, "mx8_unpack")
+        raise ValueError(f"{op} requires a device buffer")
+    _mx8_check_dtype(dtype, op)
     if buf.dtype != torch.uint8 or not buf.is_contiguous() \
             or buf.numel() != mx8_nbytes(n):
         raise ValueError(
-            f"mx8_unpack: buffer must be contiguous uint8[{mx8_nbytes(n)}] "
+            f"{op}: buffer must be contiguous uint8[{mx8_nbytes(n)}] "
             f"for {n} elements, got {buf.dtype}[{buf.numel()}]"
         )
-    lib = _require_mx8()
+    fn = _mx_entry(op)
     if out is None:
         out = torch.empty(shape, dtype=dtype, device=buf.device)
     elif not (out.is_cuda and out.dtype == dtype and out.is_contiguous()
               and out.numel() == n):
         raise ValueError(
-            f"mx8_unpack: out must be a contiguous device {dtype}[{n}]"
+            f"{op}: out must be a contiguous device {dtype}[{n}]"
         )
     _check(
-        lib.lz_mx8_unpack(
+        fn(
             ctypes.c_void_p(buf.data_ptr()),
             ctypes.c_void_p(out.data_ptr()),
             _dtype_code(dtype),
@@ -378,32 +434,37 @@ def mx8_axpby(a, wire, alpha: float = 1.0, beta: float = 1.0, dst=None):
     16-bit type first).  ``dst`` defaults to a new tensor like ``a``; it
     may be ``a`` itself (in place) and may have another of the three
     dtypes.  Returns ``dst``."""
+    return _mx_axpby("mx8_axpby", a, wire, alpha, beta, dst)
+
+
+def mxi8_axpby(a, wire, alpha: float = 1.0, beta: float = 1.0, dst=None):
+    """:func:`mx8_axpby` with the MXINT8 decode fused in: ``wire`` is an
+    MXINT8 buffer, everything else is the same."""
+    return _mx_axpby("mxi8_axpby", a, wire, alpha, beta, dst)
+
+
+def _mx_axpby(op: str, a, wire, alpha, beta, dst):
     import torch
 
     if not (a.is_cuda and wire.is_cuda):
-        raise ValueError("mx8_axpby requires device tensors")
-    _mx8_check_dtype(a.dtype, "mx8_axpby")
+        raise ValueError(f"{op} requires device tensors")
+    _mx8_check_dtype(a.dtype, op)
     n = a.numel()
     if wire.dtype != torch.uint8 or not wire.is_contiguous() \
             or wire.numel() != mx8_nbytes(n):
         raise ValueError(
-            f"mx8_axpby: wire must be contiguous uint8[{mx8_nbytes(n)}] "
+            f"{op}: wire must be contiguous uint8[{mx8_nbytes(n)}] "
             f"for {n} elements, got {wire.dtype}[{wire.numel()}]"
         )
     if dst is not None:
-        _check_dst("mx8_axpby", dst, n)
-        _mx8_check_dtype(dst.dtype, "mx8_axpby dst")
-    lib = _require_native()
-    if not _MX8_AXPBY:
-        raise NativeExtensionMissing(
-            f"{_LIB_PATH} is stale: it lacks lz_mx8_axpby; "
-            f"rebuild with `python setup.py build_ext --inplace --force`"
-        )
+        _check_dst(op, dst, n)
+        _mx8_check_dtype(dst.dtype, f"{op} dst")
+    fn = _mx_entry(op)
     x = a.detach().contiguous()
     if dst is None:
         dst = torch.empty_like(x)
     _check(
-        lib.lz_mx8_axpby(
+        fn(
             ctypes.c_void_p(x.data_ptr()),
             _dtype_code(x.dtype),
             ctypes.c_void_p(wire.data_ptr()),

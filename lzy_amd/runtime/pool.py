@@ -1214,9 +1214,9 @@ class _DriverScheduler:
         # wire format of streamed plans; the driver decides, the plan
         # carries it to the ranks (channel_wire_cast leaves plans exact)
         self._stream_wire = str(getattr(cfg, "stream_wire_cast", "") or "")
-        if self._stream_wire not in ("", "mxfp8"):
+        if self._stream_wire not in ("", "mxfp8", "mxint8"):
             raise ValueError(
-                f"stream_wire_cast must be \"\" or \"mxfp8\", "
+                f"stream_wire_cast must be \"\", \"mxfp8\" or \"mxint8\", "
                 f"got {self._stream_wire!r}"
             )
         # wire format of tensor bundles (docs/bundles.md): again the
