@@ -31,6 +31,16 @@ the two in one process:
                                                         33/32+4 B read, 4 B written (bf16)
 
 and checks that both give the same values to one unit in the last place.
+
+``--mode forward`` times the step of a merge-tree node that forwards, for
+both codecs, bf16 and f32, at a plan's chunk size and on a 1 GiB operand:
+
+  * pair   ops.mx8_axpby(a, wire_in, dst=out); ops.mx8_pack(out, out=wire_out)
+                                                        4+33/32 B read, 2+33/32 B written (bf16)
+  * fused  ops.mx8_axpby_pack(a, wire_in, dst=out, wire_out=wire_out)
+                                                        2+33/32 B read, 2+33/32 B written (bf16)
+
+and checks that both leave the same bytes in ``out`` and ``wire_out``.
 """
 import argparse
 import ctypes
@@ -128,13 +138,64 @@ def axpby_mode(args) -> None:
     print(json.dumps(result))
 
 
+def forward_mode(args) -> None:
+    """The step of a forwarding merge-tree node, per codec and accumulator
+    dtype, at the chunk a 64 MiB bf16 wired plan is cut into (8 Mi elements
+    at the default stream_chunk_mb) and on a 1 GiB operand."""
+    alpha, beta = 0.5, 0.5
+    result = {"mode": "forward", "iters": args.iters}
+    for codec, pre in _PREFIX.items():
+        pack, axpby, axpby_pack = (getattr(ops, f"{pre}_{k}")
+                                   for k in ("pack", "axpby", "axpby_pack"))
+        for dtype, name in ((torch.bfloat16, "bf16"), (torch.float32, "f32")):
+            es = 2 if dtype == torch.bfloat16 else 4
+            for label, n in (("chunk", 8 << 20), ("1GiB", (1 << 30) // es)):
+                torch.manual_seed(5)
+                a = (torch.rand(n, device="cuda") + 0.5).to(dtype)
+                wire_in = pack((torch.rand(n, device="cuda") + 0.5).to(dtype))
+                out_p, out_f = torch.empty_like(a), torch.empty_like(a)
+                wire_p, wire_f = torch.empty_like(wire_in), torch.empty_like(wire_in)
+
+                def pair():
+                    axpby(a, wire_in, alpha, beta, dst=out_p)
+                    pack(out_p, out=wire_p)
+
+                def fused():
+                    axpby_pack(a, wire_in, alpha, beta, dst=out_f, wire_out=wire_f)
+
+                iters = args.iters * (8 if label == "chunk" else 1)
+                ts = _time_alternating({"pair": pair, "fused": fused}, iters,
+                                       args.warmup)
+                w = wire_in.numel()
+                nbytes = {"pair": 3 * n * es + 2 * w, "fused": 2 * n * es + 2 * w}
+                entry = {"elems": n}
+                for k, t in ts.items():
+                    med = statistics.median(t)
+                    entry[k] = {"median_us": round(med * 1e6, 1),
+                                "min_us": round(t[0] * 1e6, 1),
+                                "max_us": round(t[-1] * 1e6, 1),
+                                "gb_per_s": round(nbytes[k] / med / 1e9, 1)}
+                    print(f"{codec} {name} {label:5s} {k:5s} median {med*1e6:9.1f} us  "
+                          f"[{t[0]*1e6:.1f} .. {t[-1]*1e6:.1f}]  "
+                          f"{nbytes[k]/med/1e9:7.0f} GB/s (read+written)")
+                entry["pair_over_fused"] = round(
+                    statistics.median(ts["pair"]) / statistics.median(ts["fused"]), 3)
+                # the plan relies on identity, not closeness
+                bits = torch.int16 if es == 2 else torch.int32
+                assert torch.equal(out_p.view(bits), out_f.view(bits))
+                assert torch.equal(wire_p, wire_f)
+                result[f"{codec}_{name}_{label}"] = entry
+                del a, wire_in, out_p, out_f, wire_p, wire_f
+    print(json.dumps(result))
+
+
 _DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
 _PREFIX = {"mxfp8": "mx8", "mxint8": "mxi8"}
 
 
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["codec", "axpby"], default="codec")
+    ap.add_argument("--mode", choices=["codec", "axpby", "forward"], default="codec")
     ap.add_argument("--codec", choices=sorted(_PREFIX), default="mxfp8")
     ap.add_argument("--melems", type=int, default=64,
                     help="axpby mode: Mi elements per buffer")
@@ -152,6 +213,9 @@ def main() -> None:
     ops._require_native()
     if args.mode == "axpby":
         axpby_mode(args)
+        return
+    if args.mode == "forward":
+        forward_mode(args)
         return
     dtype, dname = _DTYPES[args.dtype], args.dtype
     es = torch.empty(0, dtype=dtype).element_size()

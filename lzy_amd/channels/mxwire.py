@@ -23,6 +23,11 @@ same scale byte position, int8 elements (``q * 2^(b-133)``, ``0x80`` is
 NaN) — about a third of the error on tensors whose blocks have a narrow
 dynamic range.  ``wire_codec(name)`` maps a wire name (``"mxfp8"``,
 ``"mxint8"``) to its dispatching ``(pack, unpack, axpby)``.
+
+``*_axpby_pack`` / ``*_axpby2_pack`` are the step of a merge-tree node that
+forwards its result: the combine and the pack of its output, one kernel
+(``lzy_amd.ops.mx8_axpby_pack`` ...) for device tensors, the two torch
+functions above for CPU ones.  ``wire_fused(name)`` maps a wire name to them.
 """
 from __future__ import annotations
 
@@ -279,6 +284,71 @@ def mxi8_axpby(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
     return _axpby("mxi8_axpby", mxi8_axpby_torch, a, wire, alpha, beta, dst)
 
 
+def _axpby_pack(op: str, combine_torch: Callable, pack_torch: Callable, a, second,
+                alpha, beta, dst, wire_out):
+    """The step of a forwarding merge-tree node: ``(dst, pack(dst))``.  One
+    kernel for device tensors; on CPU the combine and the pack it replaces,
+    so the result is theirs bit for bit."""
+    if _native(a):
+        from lzy_amd import ops
+
+        return getattr(ops, op)(a, second, alpha, beta, dst=dst, wire_out=wire_out)
+    r = combine_torch(a, second, alpha, beta, a.dtype if dst is None else dst.dtype)
+    if dst is None:
+        dst = r
+    else:
+        if dst.shape != a.shape:
+            raise ValueError(
+                f"{op}: dst has shape {tuple(dst.shape)}, "
+                f"expected {tuple(a.shape)}"
+            )
+        dst.copy_(r)
+    packed = pack_torch(dst)
+    if wire_out is None:
+        return dst, packed
+    wire_out.copy_(packed)
+    return dst, wire_out
+
+
+def _axpby2_torch(a, b, alpha, beta, out_dtype):
+    # the combine of an unwired plan step on tensors the kernels do not serve
+    return torch.add(a * alpha, b, alpha=beta).to(out_dtype)
+
+
+def mx8_axpby_pack(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
+                   beta: float = 1.0, dst: Optional[torch.Tensor] = None,
+                   wire_out: Optional[torch.Tensor] = None):
+    """``dst = alpha*a + beta*decode(wire)`` and ``wire_out = pack(dst)``;
+    returns ``(dst, wire_out)``."""
+    return _axpby_pack("mx8_axpby_pack", mx8_axpby_torch, mx8_pack_torch, a, wire,
+                       alpha, beta, dst, wire_out)
+
+
+def mxi8_axpby_pack(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
+                    beta: float = 1.0, dst: Optional[torch.Tensor] = None,
+                    wire_out: Optional[torch.Tensor] = None):
+    """:func:`mx8_axpby_pack` for MXINT8 buffers."""
+    return _axpby_pack("mxi8_axpby_pack", mxi8_axpby_torch, mxi8_pack_torch, a, wire,
+                       alpha, beta, dst, wire_out)
+
+
+def mx8_axpby2_pack(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
+                    beta: float = 1.0, dst: Optional[torch.Tensor] = None,
+                    wire_out: Optional[torch.Tensor] = None):
+    """``dst = alpha*a + beta*b`` and ``wire_out = pack(dst)``; returns
+    ``(dst, wire_out)``."""
+    return _axpby_pack("mx8_axpby2_pack", _axpby2_torch, mx8_pack_torch, a, b,
+                       alpha, beta, dst, wire_out)
+
+
+def mxi8_axpby2_pack(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
+                     beta: float = 1.0, dst: Optional[torch.Tensor] = None,
+                     wire_out: Optional[torch.Tensor] = None):
+    """:func:`mx8_axpby2_pack` with an MXINT8 ``wire_out``."""
+    return _axpby_pack("mxi8_axpby2_pack", _axpby2_torch, mxi8_pack_torch, a, b,
+                       alpha, beta, dst, wire_out)
+
+
 # wire name (channel_wire_cast, stream_wire_cast, a plan's "wire") -> the
 # dispatching (pack, unpack, axpby); both codecs share mx8_nbytes
 _WIRE_CODECS = {
@@ -286,9 +356,20 @@ _WIRE_CODECS = {
     "mxint8": (mxi8_pack, mxi8_unpack, mxi8_axpby),
 }
 MX_WIRES = tuple(_WIRE_CODECS)
+# ... -> the dispatching (axpby_pack, axpby2_pack) of a forwarding node
+_WIRE_FUSED = {
+    "mxfp8": (mx8_axpby_pack, mx8_axpby2_pack),
+    "mxint8": (mxi8_axpby_pack, mxi8_axpby2_pack),
+}
 
 
 def wire_codec(wire: str) -> Tuple[Callable, Callable, Callable]:
     if wire not in _WIRE_CODECS:
         raise ValueError(f"wire must be one of {MX_WIRES}, got {wire!r}")
     return _WIRE_CODECS[wire]
+
+
+def wire_fused(wire: str) -> Tuple[Callable, Callable]:
+    if wire not in _WIRE_FUSED:
+        raise ValueError(f"wire must be one of {MX_WIRES}, got {wire!r}")
+    return _WIRE_FUSED[wire]

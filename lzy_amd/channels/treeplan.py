@@ -351,6 +351,8 @@ def run_stream_plan(
         from lzy_amd.channels import mxwire
 
         wire_pack, _, wire_axpby = mxwire.wire_codec(plan["wire"])
+        # a node that forwards combines and re-encodes in one step
+        wire_axpby_pack, wire_axpby2_pack = mxwire.wire_fused(plan["wire"])
         wper = mxwire.mx8_nbytes(per)  # chunk j starts at byte j * wper
 
     def flat_entry(eid: str) -> torch.Tensor:
@@ -468,13 +470,16 @@ def run_stream_plan(
         send_works: List[Any] = []
         staged: List[torch.Tensor] = []  # packed / host-staged keepalive
 
-        def issue_send(t: torch.Tensor, dst: int, topo: int) -> None:
+        def issue_send(t: torch.Tensor, dst: int, topo: int,
+                       packed: bool = False) -> None:
             stats["sends"] += 1
             tg = edge_tag(topo)
             if wired:
                 # pack where the chunk lives (the kernel, for a device
-                # chunk), THEN stage: only packed bytes cross PCIe
-                t = wire_pack(t)
+                # chunk), THEN stage: only packed bytes cross PCIe.
+                # `packed`: t is the chunk's wire buffer already.
+                if not packed:
+                    t = wire_pack(t)
                 staged.append(t)
             stats["wire_bytes"] += t.numel() * t.element_size()
             if host_stage and t.is_cuda:
@@ -493,11 +498,14 @@ def run_stream_plan(
         except Exception:  # pragma: no cover - ops ext missing
             use_hip = False
 
-        def combine(dst_c, a_c, b_c, alpha, beta):
-            if (
+        def hip_combine(dst_c) -> bool:
+            return (
                 dst_c.is_cuda and use_hip
                 and dst_c.dtype in (torch.float32, torch.float16, torch.bfloat16)
-            ):
+            )
+
+        def combine(dst_c, a_c, b_c, alpha, beta):
+            if hip_combine(dst_c):
                 from lzy_amd import ops as _ops
 
                 _ops.axpby(a_c, b_c, alpha, beta, dst=dst_c)
@@ -517,6 +525,11 @@ def run_stream_plan(
                     if st["local_is_entry"] else outs[st["local"]]
                 )
                 out = outs[st["out"]]
+                # a wired node that forwards (docs/mxwire.md, "Forwarding
+                # nodes"): combine and pack(out chunk) in one step, the one
+                # packed buffer then goes to every destination
+                fwd = None
+                fuse = wired and bool(st["send_to"])
                 if st["remote_src"] is not None:
                     src = st["remote_src"]
                     sts = seq_by_src[src]
@@ -528,7 +541,10 @@ def run_stream_plan(
                     b_c = recv_buf[st["topo"]][rs:re_]
                     if host_stage:
                         b_c = b_c.to(a.device)
-                    if wired:
+                    if fuse:
+                        _, fwd = wire_axpby_pack(a[s:e], b_c, st["alpha"],
+                                                 st["beta"], dst=out[s:e])
+                    elif wired:
                         # decode fused into the combine: no plan-dtype
                         # temporary of the received chunk
                         wire_axpby(a[s:e], b_c, st["alpha"], st["beta"],
@@ -540,9 +556,16 @@ def run_stream_plan(
                         local2_flat[st["topo"]]
                         if st["local2_is_entry"] else outs[st["local2"]]
                     )
-                    combine(out[s:e], a[s:e], b[s:e], st["alpha"], st["beta"])
+                    if fuse and hip_combine(out[s:e]):
+                        _, fwd = wire_axpby2_pack(a[s:e], b[s:e], st["alpha"],
+                                                  st["beta"], dst=out[s:e])
+                    else:
+                        combine(out[s:e], a[s:e], b[s:e], st["alpha"], st["beta"])
                 for dst, fwd_topo in st["send_to"]:
-                    issue_send(out[s:e], dst, fwd_topo)
+                    if fwd is not None:
+                        issue_send(fwd, dst, fwd_topo, packed=True)
+                    else:
+                        issue_send(out[s:e], dst, fwd_topo)
 
         for w in send_works:
             w.wait()

@@ -24,6 +24,9 @@ _load_error: Optional[str] = None
 _MX8 = False  # libhipops.so exports lz_mx8_pack / lz_mx8_unpack
 _MX8_AXPBY = False  # ... and lz_mx8_axpby (the fused decode-combine)
 _MXI8 = False  # ... and lz_mxi8_pack / lz_mxi8_unpack / lz_mxi8_axpby (MXINT8)
+# ... and lz_mx8_axpby_pack / lz_mx8_axpby2_pack and their mxi8 twins (the
+# fused combine + re-encode of a forwarding merge-tree node)
+_MX_AXPBY_PACK = False
 _SEGCOPY = False  # ... and lz_segcopy (the packed-bundle gather/scatter)
 # bytes per tile of the segmented copy — LZ_SEG_TILE in hipops.hip
 SEGCOPY_TILE = 16384
@@ -164,6 +167,27 @@ def _try_load() -> Optional[ctypes.CDLL]:
         _MXI8 = True
     except AttributeError:
         _MXI8 = False
+    global _MX_AXPBY_PACK
+    try:
+        for name in ("lz_mx8_axpby_pack", "lz_mxi8_axpby_pack"):
+            fn = getattr(lib, name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = [
+                ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
+                ctypes.c_float, ctypes.c_void_p,
+            ]
+        for name in ("lz_mx8_axpby2_pack", "lz_mxi8_axpby2_pack"):
+            fn = getattr(lib, name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = [
+                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
+                ctypes.c_float, ctypes.c_void_p,
+            ]
+        _MX_AXPBY_PACK = True
+    except AttributeError:
+        _MX_AXPBY_PACK = False
     global _SEGCOPY
     try:
         lib.lz_segcopy.restype = ctypes.c_int
@@ -306,10 +330,14 @@ def _require_mx8() -> ctypes.CDLL:
 def _mx_entry(op: str):
     """The C entry point ``lz_<op>`` of an ``mx8_*`` / ``mxi8_*`` wrapper; a
     library built before it raises, whatever else it can still do."""
-    if op.startswith("mx8_") and op != "mx8_axpby":
+    if op.startswith("mx8_") and "axpby" not in op:
         return getattr(_require_mx8(), "lz_" + op)
     lib = _require_native()
-    if not (_MX8_AXPBY if op == "mx8_axpby" else _MXI8):
+    if op.endswith("_pack") and "axpby" in op:
+        present = _MX_AXPBY_PACK
+    else:
+        present = _MX8_AXPBY if op == "mx8_axpby" else _MXI8
+    if not present:
         raise NativeExtensionMissing(
             f"{_LIB_PATH} is stale: it lacks lz_{op}; "
             f"rebuild with `python setup.py build_ext --inplace --force`"
@@ -477,6 +505,95 @@ def _mx_axpby(op: str, a, wire, alpha, beta, dst):
         )
     )
     return dst
+
+
+def mx8_axpby_pack(a, wire, alpha: float = 1.0, beta: float = 1.0, dst=None,
+                   wire_out=None):
+    """:func:`mx8_axpby` and :func:`mx8_pack` of its result in one launch:
+    the step of a merge-tree node that forwards (docs/mxwire.md,
+    "Forwarding nodes").  Returns ``(dst, wire_out)``.
+
+    ``dst`` is bit for bit what ``mx8_axpby`` writes, ``wire_out`` byte for
+    byte ``mx8_pack(dst)``: the encoder sees the value already rounded to
+    ``dst``'s dtype.  ``dst`` may be ``a``; ``wire_out`` (a contiguous device
+    ``uint8[mx8_nbytes(a.numel())]``, new when not given) must not overlap
+    any other argument."""
+    return _mx_axpby_pack("mx8_axpby_pack", a, wire, alpha, beta, dst, wire_out)
+
+
+def mxi8_axpby_pack(a, wire, alpha: float = 1.0, beta: float = 1.0, dst=None,
+                    wire_out=None):
+    """:func:`mx8_axpby_pack` for MXINT8: ``wire`` and ``wire_out`` are both
+    MXINT8 buffers."""
+    return _mx_axpby_pack("mxi8_axpby_pack", a, wire, alpha, beta, dst, wire_out)
+
+
+def mx8_axpby2_pack(a, b, alpha: float = 1.0, beta: float = 1.0, dst=None,
+                    wire_out=None):
+    """:func:`axpby` of two plain operands of one dtype and :func:`mx8_pack`
+    of its result in one launch (a forwarding node whose inputs are both
+    local).  Returns ``(dst, wire_out)``; see :func:`mx8_axpby_pack`."""
+    return _mx_axpby_pack("mx8_axpby2_pack", a, b, alpha, beta, dst, wire_out)
+
+
+def mxi8_axpby2_pack(a, b, alpha: float = 1.0, beta: float = 1.0, dst=None,
+                     wire_out=None):
+    """:func:`mx8_axpby2_pack` with an MXINT8 ``wire_out``."""
+    return _mx_axpby_pack("mxi8_axpby2_pack", a, b, alpha, beta, dst, wire_out)
+
+
+def _mx_axpby_pack(op: str, a, second, alpha, beta, dst, wire_out):
+    import torch
+
+    plain = "axpby2" in op  # second operand: a tensor like a, or a wire
+    if not (a.is_cuda and second.is_cuda):
+        raise ValueError(f"{op} requires device tensors")
+    _mx8_check_dtype(a.dtype, op)
+    n = a.numel()
+    nbytes = mx8_nbytes(n)
+    if plain:
+        if second.numel() != n or second.dtype != a.dtype:
+            raise ValueError(f"{op}: shape/dtype mismatch")
+    elif second.dtype != torch.uint8 or not second.is_contiguous() \
+            or second.numel() != nbytes:
+        raise ValueError(
+            f"{op}: wire must be contiguous uint8[{nbytes}] "
+            f"for {n} elements, got {second.dtype}[{second.numel()}]"
+        )
+    if dst is not None:
+        _check_dst(op, dst, n)
+        _mx8_check_dtype(dst.dtype, f"{op} dst")
+    if wire_out is not None:
+        if not (wire_out.is_cuda and wire_out.dtype == torch.uint8
+                and wire_out.is_contiguous() and wire_out.numel() == nbytes):
+            raise ValueError(
+                f"{op}: wire_out must be a contiguous device uint8[{nbytes}]"
+            )
+        if not plain and wire_out.data_ptr() == second.data_ptr():
+            raise ValueError(f"{op}: wire_out must not share storage with wire")
+    fn = _mx_entry(op)
+    x = a.detach().contiguous()
+    y = second.detach().contiguous()
+    if dst is None:
+        dst = torch.empty_like(x)
+    if wire_out is None:
+        wire_out = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ptr = ctypes.c_void_p
+    head = (ptr(x.data_ptr()), ptr(y.data_ptr()), _dtype_code(x.dtype)) if plain \
+        else (ptr(x.data_ptr()), _dtype_code(x.dtype), ptr(y.data_ptr()))
+    _check(
+        fn(
+            *head,
+            ptr(dst.data_ptr()),
+            _dtype_code(dst.dtype),
+            ptr(wire_out.data_ptr()),
+            n,
+            ctypes.c_float(alpha),
+            ctypes.c_float(beta),
+            ptr(_current_stream_ptr()),
+        )
+    )
+    return dst, wire_out
 
 
 # ---------------------------------------------------------------------------

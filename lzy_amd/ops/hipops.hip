@@ -247,7 +247,11 @@ __device__ __forceinline__ uint32_t lz_mx8_encode4(const float* f, float mult) {
 // here is held bit for bit to a reference.
 // ---------------------------------------------------------------------------
 enum LzMxCodec : int { LZ_MXFP8 = 0, LZ_MXINT8 = 1 };
+#if defined(__HIP_DEVICE_COMPILE__)
 #define LZ_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define LZ_NO_PK_F32  // a device feature: the host pass would warn and ignore it
+#endif
 
 // scale byte of a block from the raw bits of its finite amax (>= 0): the
 // smallest b with rne(amax * 2^(133-b)) <= 127, capped at 254.  With b = E
@@ -1438,6 +1442,276 @@ extern "C" hipError_t lz_mxi8_axpby(const void* a, int a_dtype, const void* wire
                                     float beta, void* stream) {
     return lz_mx_axpby_launch<LZ_MXINT8>(a, a_dtype, wire_u8, dst, dst_dtype, n, alpha,
                                          beta, stream);
+}
+
+// ---------------------------------------------------------------------------
+// mx8_axpby_pack / mx8_axpby2_pack: the step of a merge-tree node that
+// forwards (docs/mxwire.md, "Forwarding nodes"), in one pass:
+//   dst      = cast(alpha*a + beta*x)   x = decode(wire_in), or a plain b
+//   wire_out = pack(dst)
+// The combine followed by a pack of its result moves ~8 B/element of bf16
+// through HBM in two launches; here the value is encoded while it is still in
+// registers: ~6 B/element (2 + 33/32 read, 2 + 33/32 written), one launch.
+//
+// dst is lz_mx8_axpby's (axpby_kernel's) value bit for bit, and wire_out is
+// byte for byte what lz_mx8_pack makes of that dst: the encoder is handed the
+// value already rounded to DstT, widened back to fp32, never the unrounded
+// FMA result.  Positions >= n of the last block enter it as +0.0, whatever
+// the padding bytes of wire_in decode to and whatever beta is.
+//
+// The encode half crosses lanes (lz_mx8_emit), so the loop has
+// lz_mx_pack_body's shape: g0 and every branch on it are wave-uniform, and
+// lanes whose group lies past the tensor go through the encoder with zeros.
+// Two groups per trip; on the unguarded path the payload words, the scale
+// bytes and the 16 B loads of a (and b) of both groups issue before any is
+// consumed.  dst may be a (a lane reads its 8 elements before it writes
+// them); wire_out must not overlap any other argument.
+//
+// Both codecs are compiled without packed fp32 VALU ops (see mxi8 above).
+// ---------------------------------------------------------------------------
+
+// the second operand of one group, loaded and not yet consumed: the payload
+// words and scale byte of a wire (WIRE), or 8 plain elements as fp32
+struct LzMxSecond {
+    uint32_t w[2], b;
+    float f[8];
+};
+
+template <typename SrcT, bool WIRE, bool ALIGNED, bool FULL>
+__device__ __forceinline__ void lz_mxf_fetch(const void* src2,
+                                             const uint8_t* __restrict__ scales_in,
+                                             int64_t g, int64_t n, LzMxSecond& s) {
+    if constexpr (WIRE) {
+        // payload bytes of the padded tail exist: [0, 32*nblk)
+        lz_mx8_dec_load<ALIGNED>(static_cast<const uint8_t*>(src2), scales_in, g, s.w,
+                                 s.b);
+    } else {
+        lz_mx8_load<SrcT, FULL>(static_cast<const SrcT*>(src2), g * 8, n, s.f);
+    }
+}
+
+// combine one group, store it to dst and leave in r what the encoder sees:
+// the stored value as fp32, +0.0 at positions >= n.  FULL: all 8 elements
+// lie inside [0, n) and dst + e0 is 16 B-aligned.
+//
+// TWO_STEP (f16 dst only): the combine kernels reach an f16 two ways.  Where
+// they store a whole group, the fp32 FMA result is converted (two roundings);
+// elsewhere the compiler fuses FMA and convert into v_fma_mixlo_f16, which
+// rounds the exact sum once.  The two differ on about one element in 2^14.
+// dst must be the combine kernels' bit for bit, so this kernel takes, group
+// by group, the way they take (lz_mxf_two_step below); the empty asm keeps
+// the fp32 result a value of its own, which rules the fused form out.
+template <typename DstT, bool WIRE, bool FULL, bool TWO_STEP, int CODEC>
+__device__ __forceinline__ void lz_mxf_combine(const float (&fa)[8], const LzMxSecond& s,
+                                               DstT* dst, int64_t e0, int64_t n,
+                                               float alpha, float beta, float (&r)[8]) {
+    constexpr int V = 8;
+    float x[V];
+    if constexpr (!WIRE) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) x[k] = s.f[k];
+    } else if constexpr (CODEC == LZ_MXINT8) {
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            x[k] = lz_mxi8_dequant(s.w[k >> 2], k & 3, (int)s.b - 133);
+    } else {
+        lz_mx8_decode8(s.w[0], s.w[1], lz_mx8_mult(s.b), x);
+    }
+    DstT y[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        float t = fmaf(fa[k], alpha, x[k] * beta);
+        if constexpr (TWO_STEP && std::is_same<DstT, __half>::value)
+            asm volatile("" : "+v"(t));
+        y[k] = lz_from_float<DstT>(t);
+        r[k] = (FULL || e0 + k < n) ? lz_to_float<DstT>(y[k]) : 0.f;
+    }
+    if (FULL) {
+        LzVec16 q[sizeof(DstT) * V / 16];
+        __builtin_memcpy(q, y, sizeof(y));
+        LzVec16* p = reinterpret_cast<LzVec16*>(dst + e0);
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(DstT) * V / 16); ++k) p[k] = q[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            if (e0 + k < n) dst[e0 + k] = y[k];
+    }
+}
+
+// how the kernel this one stands in for rounds a whole group (all 8 elements
+// inside [0, n)) to f16.  lz_mx_axpby_body: two steps on its 16 B-store path
+// of the MXFP8 kernels, fused everywhere in the MXINT8 ones (compiled without
+// packed fp32 ops).  axpby_kernel: two steps on every whole group, aligned
+// or not.  A group cut by n is fused in all of them.
+template <bool WIRE, bool FULL, int CODEC>
+constexpr bool lz_mxf_two_step() {
+    return WIRE ? (FULL && CODEC == LZ_MXFP8) : true;
+}
+
+// one group on the guarded path (the tail, and element-aligned views).  The
+// branch is per lane and closes before the caller's cross-lane encode: a
+// lane whose group lies past n loads and stores nothing and hands on +0.0.
+template <typename SrcT, typename DstT, bool WIRE, bool ALIGNED, int CODEC>
+__device__ __forceinline__ void lz_mxf_one(const SrcT* a, const void* src2,
+                                           const uint8_t* __restrict__ scales_in,
+                                           DstT* dst, int64_t g, int64_t n, float alpha,
+                                           float beta, float (&r)[8]) {
+    const int64_t e0 = g * 8;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = 0.f;
+    if (e0 >= n) return;
+    LzMxSecond s;
+    float fa[8];
+    if (ALIGNED && e0 + 8 <= n) {
+        lz_mxf_fetch<SrcT, WIRE, ALIGNED, true>(src2, scales_in, g, n, s);
+        lz_mx8_load<SrcT, true>(a, e0, n, fa);
+        lz_mxf_combine<DstT, WIRE, true, lz_mxf_two_step<WIRE, true, CODEC>(), CODEC>(
+            fa, s, dst, e0, n, alpha, beta, r);
+    } else {
+        lz_mxf_fetch<SrcT, WIRE, ALIGNED, false>(src2, scales_in, g, n, s);
+        lz_mx8_load<SrcT, false>(a, e0, n, fa);
+        if (!ALIGNED && e0 + 8 <= n && lz_mxf_two_step<WIRE, false, CODEC>())
+            lz_mxf_combine<DstT, WIRE, false, true, CODEC>(fa, s, dst, e0, n, alpha, beta,
+                                                           r);
+        else
+            lz_mxf_combine<DstT, WIRE, false, false, CODEC>(fa, s, dst, e0, n, alpha,
+                                                            beta, r);
+    }
+}
+
+template <typename SrcT, typename DstT, bool WIRE, bool ALIGNED, int CODEC>
+__global__ void __launch_bounds__(LZ_BLOCK) LZ_NO_PK_F32
+mx_axpby_pack_kernel(const SrcT* a, const void* src2, DstT* dst,
+                     uint8_t* __restrict__ wire_out, int64_t n, float alpha, float beta) {
+    const uint32_t bdim = blockDim.x;
+    const int64_t nblk = (n + 31) >> 5;
+    const int64_t ngroups = nblk * 4;
+    const uint8_t* __restrict__ scales_in =
+        WIRE ? static_cast<const uint8_t*>(src2) + nblk * 32 : nullptr;
+    uint8_t* __restrict__ scales_out = wire_out + nblk * 32;
+    const int64_t stride = (int64_t)gridDim.x * bdim;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+
+    for (int64_t g0 = (int64_t)blockIdx.x * bdim + wave * 64; g0 < ngroups;
+         g0 += 2 * stride) {
+        const int64_t ga = g0 + lane, gb = ga + stride;
+        float ra[8], rb[8];
+        if (ALIGNED && (g0 + stride + 64) * 8 <= n) {  // both groups of all 64 lanes whole
+            LzMxSecond sa, sb;
+            float fa[8], fb[8];
+            lz_mxf_fetch<SrcT, WIRE, true, true>(src2, scales_in, ga, n, sa);
+            lz_mxf_fetch<SrcT, WIRE, true, true>(src2, scales_in, gb, n, sb);
+            lz_mx8_load<SrcT, true>(a, ga * 8, n, fa);
+            lz_mx8_load<SrcT, true>(a, gb * 8, n, fb);
+            constexpr bool TS = lz_mxf_two_step<WIRE, true, CODEC>();
+            lz_mxf_combine<DstT, WIRE, true, TS, CODEC>(fa, sa, dst, ga * 8, n, alpha, beta,
+                                                        ra);
+            lz_mxf_combine<DstT, WIRE, true, TS, CODEC>(fb, sb, dst, gb * 8, n, alpha, beta,
+                                                        rb);
+            lz_mx8_emit<true, true, CODEC>(ra, ga, lane, ngroups, nblk, wire_out,
+                                           scales_out);
+            lz_mx8_emit<true, true, CODEC>(rb, gb, lane, ngroups, nblk, wire_out,
+                                           scales_out);
+        } else {
+            const bool two = g0 + stride < ngroups;
+            lz_mxf_one<SrcT, DstT, WIRE, ALIGNED, CODEC>(a, src2, scales_in, dst, ga, n,
+                                                         alpha, beta, ra);
+            lz_mx8_emit<ALIGNED, false, CODEC>(ra, ga, lane, ngroups, nblk, wire_out,
+                                               scales_out);
+            if (two) {
+                lz_mxf_one<SrcT, DstT, WIRE, ALIGNED, CODEC>(a, src2, scales_in, dst, gb,
+                                                             n, alpha, beta, rb);
+                lz_mx8_emit<ALIGNED, false, CODEC>(rb, gb, lane, ngroups, nblk, wire_out,
+                                                   scales_out);
+            }
+        }
+    }
+}
+
+// a, dst: n elements of a_dtype / dst_dtype (both f32/f16/bf16); src2: the
+// wire of n elements (WIRE) or n more elements of a_dtype; wire_out:
+// 33*ceil(n/32) bytes.  dst == a is allowed; wire_out overlaps nothing.
+template <int CODEC, bool WIRE>
+static hipError_t lz_mx_axpby_pack_launch(const void* a, int a_dtype, const void* src2,
+                                          void* dst, int dst_dtype, void* wire_out,
+                                          int64_t n, float alpha, float beta,
+                                          void* stream) {
+    if (a_dtype != LZ_F32 && a_dtype != LZ_F16 && a_dtype != LZ_BF16)
+        return hipErrorInvalidValue;
+    if (dst_dtype != LZ_F32 && dst_dtype != LZ_F16 && dst_dtype != LZ_BF16)
+        return hipErrorInvalidValue;
+    if (n < 0) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    const int blocks = lz_mx8_grid(n);
+    const bool aligned = (((uintptr_t)a & 15) == 0) && (((uintptr_t)dst & 15) == 0) &&
+                         (((uintptr_t)src2 & (WIRE ? 7 : 15)) == 0) &&
+                         (((uintptr_t)wire_out & 7) == 0);
+#define LZ_MXF_LAUNCH(AL)                                                       \
+    hipLaunchKernelGGL((mx_axpby_pack_kernel<S, D, WIRE, AL, CODEC>), dim3(blocks), \
+                       dim3(LZ_BLOCK), 0, s, (const S*)a, src2, (D*)dst,        \
+                       (uint8_t*)wire_out, n, alpha, beta)
+#define LZ_MXF_DST(SrcT, code, DstT)                                            \
+    case code: {                                                                \
+        using S = SrcT;                                                         \
+        using D = DstT;                                                         \
+        if (aligned) LZ_MXF_LAUNCH(true);                                       \
+        else LZ_MXF_LAUNCH(false);                                              \
+        break;                                                                  \
+    }
+#define LZ_MXF_SRC(scode, SrcT)                                                 \
+    case scode:                                                                 \
+        switch (dst_dtype) {                                                    \
+            LZ_MXF_DST(SrcT, LZ_F32, float)                                     \
+            LZ_MXF_DST(SrcT, LZ_F16, __half)                                    \
+            LZ_MXF_DST(SrcT, LZ_BF16, __hip_bfloat16)                           \
+            default: return hipErrorInvalidValue;                               \
+        }                                                                       \
+        break;
+    switch (a_dtype) {
+        LZ_MXF_SRC(LZ_F32, float)
+        LZ_MXF_SRC(LZ_F16, __half)
+        LZ_MXF_SRC(LZ_BF16, __hip_bfloat16)
+        default: return hipErrorInvalidValue;
+    }
+#undef LZ_MXF_SRC
+#undef LZ_MXF_DST
+#undef LZ_MXF_LAUNCH
+    return hipGetLastError();
+}
+
+extern "C" hipError_t lz_mx8_axpby_pack(const void* a, int a_dtype, const void* wire_in,
+                                        void* dst, int dst_dtype, void* wire_out,
+                                        int64_t n, float alpha, float beta,
+                                        void* stream) {
+    return lz_mx_axpby_pack_launch<LZ_MXFP8, true>(a, a_dtype, wire_in, dst, dst_dtype,
+                                                   wire_out, n, alpha, beta, stream);
+}
+
+extern "C" hipError_t lz_mxi8_axpby_pack(const void* a, int a_dtype, const void* wire_in,
+                                         void* dst, int dst_dtype, void* wire_out,
+                                         int64_t n, float alpha, float beta,
+                                         void* stream) {
+    return lz_mx_axpby_pack_launch<LZ_MXINT8, true>(a, a_dtype, wire_in, dst, dst_dtype,
+                                                    wire_out, n, alpha, beta, stream);
+}
+
+extern "C" hipError_t lz_mx8_axpby2_pack(const void* a, const void* b, int src_dtype,
+                                         void* dst, int dst_dtype, void* wire_out,
+                                         int64_t n, float alpha, float beta,
+                                         void* stream) {
+    return lz_mx_axpby_pack_launch<LZ_MXFP8, false>(a, src_dtype, b, dst, dst_dtype,
+                                                    wire_out, n, alpha, beta, stream);
+}
+
+extern "C" hipError_t lz_mxi8_axpby2_pack(const void* a, const void* b, int src_dtype,
+                                          void* dst, int dst_dtype, void* wire_out,
+                                          int64_t n, float alpha, float beta,
+                                          void* stream) {
+    return lz_mx_axpby_pack_launch<LZ_MXINT8, false>(a, src_dtype, b, dst, dst_dtype,
+                                                     wire_out, n, alpha, beta, stream);
 }
 
 // ---------------------------------------------------------------------------
