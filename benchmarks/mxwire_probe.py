@@ -1,7 +1,9 @@
-"""Byte-rate probe for the block-scaled 8-bit wire kernels (run on an
-MI355X).  ``--codec mxint8`` times the ``mxi8_*`` kernels in place of the
-``mx8_*`` ones named below; ``--compare-lib`` always adds the other build's
-``lz_mx8_*``, which move the same bytes.
+"""Byte-rate probe for the block-scaled wire kernels (run on an MI355X).
+``--codec mxint8`` times the ``mxi8_*`` kernels in place of the ``mx8_*``
+ones named below; ``--compare-lib`` always adds the other build's
+``lz_mx8_*``, which move the same bytes.  ``--codec mxfp4`` times
+``mx4_pack``, ``mx4_unpack`` and ``mx4_axpby`` (17/32 B per element on the
+wire side) and, in the same rounds, this build's ``mx8_*`` three.
 
 On a 1 GiB bf16 buffer (``--dtype f16`` / ``f32``: as many bytes of that
 type), times in one process, interleaved round-robin:
@@ -79,7 +81,7 @@ def _time_alternating(cases, iters, warmup):
 def axpby_mode(args) -> None:
     n = args.melems << 20
     alpha, beta = 0.5, 0.5
-    wire = torch.empty(ops.mx8_nbytes(n), device="cuda", dtype=torch.uint8)
+    wire = torch.empty(_nbytes(args.codec, n), device="cuda", dtype=torch.uint8)
     src = torch.empty(n, device="cuda", dtype=torch.bfloat16)
     ops.fill_pattern(src, seed=3, mask16=0x3FFF)  # finite positive bf16
     pre = _PREFIX[args.codec]
@@ -144,7 +146,8 @@ def forward_mode(args) -> None:
     at the default stream_chunk_mb) and on a 1 GiB operand."""
     alpha, beta = 0.5, 0.5
     result = {"mode": "forward", "iters": args.iters}
-    for codec, pre in _PREFIX.items():
+    for codec in ("mxfp8", "mxint8"):  # the codecs with a fused forwarding kernel
+        pre = _PREFIX[codec]
         pack, axpby, axpby_pack = (getattr(ops, f"{pre}_{k}")
                                    for k in ("pack", "axpby", "axpby_pack"))
         for dtype, name in ((torch.bfloat16, "bf16"), (torch.float32, "f32")):
@@ -190,7 +193,11 @@ def forward_mode(args) -> None:
 
 
 _DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
-_PREFIX = {"mxfp8": "mx8", "mxint8": "mxi8"}
+_PREFIX = {"mxfp8": "mx8", "mxint8": "mxi8", "mxfp4": "mx4"}
+
+
+def _nbytes(codec: str, n: int) -> int:
+    return ops.mx4_nbytes(n) if codec == "mxfp4" else ops.mx8_nbytes(n)
 
 
 def main() -> None:
@@ -223,7 +230,7 @@ def main() -> None:
     src = torch.empty(n, device="cuda", dtype=dtype)
     # every 16-bit lane <= 0x3FFF: finite and positive in all three types
     ops.fill_pattern(src, seed=3, mask16=0x3FFF)
-    wire = torch.empty(ops.mx8_nbytes(n), device="cuda", dtype=torch.uint8)
+    wire = torch.empty(_nbytes(args.codec, n), device="cuda", dtype=torch.uint8)
     fp8 = torch.empty(n, device="cuda", dtype=torch.float8_e4m3fn)
     back = torch.empty(n, device="cuda", dtype=dtype)
     pre = _PREFIX[args.codec]
@@ -238,6 +245,19 @@ def main() -> None:
         f"cast_{dname}_to_e4m3": (lambda: ops.cast_copy(src, fp8), es * n + n),
         f"cast_e4m3_to_{dname}": (lambda: ops.cast_copy(fp8, back), n + es * n),
     }
+    if args.codec == "mxfp4":
+        # the 8-bit kernels and both decode-combines, in the same rounds
+        wire8 = ops.mx8_pack(src)
+        acc = torch.empty_like(src)
+        cases.update({
+            "mx8_pack": (lambda: ops.mx8_pack(src, out=wire8), es * n + wire8.numel()),
+            "mx8_unpack": (lambda: ops.mx8_unpack(wire8, n, dtype, out=back),
+                           wire8.numel() + es * n),
+            "mx4_axpby": (lambda: ops.mx4_axpby(src, wire, 0.5, 0.5, dst=acc),
+                          2 * es * n + wire.numel()),
+            "mx8_axpby": (lambda: ops.mx8_axpby(src, wire8, 0.5, 0.5, dst=acc),
+                          2 * es * n + wire8.numel()),
+        })
     if args.compare_lib:
         other = ctypes.CDLL(args.compare_lib)
         other.lz_mx8_unpack.restype = ctypes.c_int
@@ -249,7 +269,7 @@ def main() -> None:
                                       ctypes.c_void_p, ctypes.c_int64,
                                       ctypes.c_void_p]
         back2 = torch.empty_like(back)
-        wire2 = torch.empty_like(wire)
+        wire2 = torch.empty(ops.mx8_nbytes(n), device="cuda", dtype=torch.uint8)
         ops.mx8_pack(src, out=wire2)  # what the other build's unpack reads
         code = ops._dtype_code(dtype)
 
@@ -263,8 +283,8 @@ def main() -> None:
                                       ops._current_stream_ptr())
             assert err == 0, err
 
-        cases["mx8_pack@compare-lib"] = (other_pack, es * n + wire.numel())
-        cases["mx8_unpack@compare-lib"] = (other_unpack, wire.numel() + es * n)
+        cases["mx8_pack@compare-lib"] = (other_pack, es * n + wire2.numel())
+        cases["mx8_unpack@compare-lib"] = (other_unpack, wire2.numel() + es * n)
     for _ in range(args.warmup):
         for fn, _b in cases.values():
             fn()
@@ -314,6 +334,7 @@ def main() -> None:
     x = x.to(dtype)
     got = pack(x.cuda()).cpu()
     want = getattr(mxwire, f"{pre}_pack_torch")(x)
+    m = got.numel() - m // 32  # payload bytes; the scale bytes follow
     result["payload_mismatch_fraction"] = (got[:m] != want[:m]).float().mean().item()
     result["scale_mismatches"] = int((got[m:] != want[m:]).sum().item())
     print(f"payload mismatch fraction vs torch codec: "

@@ -1,4 +1,4 @@
-"""Block-scaled 8-bit wire codecs (OCP MXFP8 and MXINT8; format spec:
+"""Block-scaled wire codecs (OCP MXFP8, MXINT8 and MXFP4; format spec:
 docs/mxwire.md).
 
 Every 32 consecutive elements share one power-of-two scale byte (E8M0)
@@ -28,6 +28,12 @@ dynamic range.  ``wire_codec(name)`` maps a wire name (``"mxfp8"``,
 forwards its result: the combine and the pack of its output, one kernel
 (``lzy_amd.ops.mx8_axpby_pack`` ...) for device tensors, the two torch
 functions above for CPU ones.  ``wire_fused(name)`` maps a wire name to them.
+
+The ``mx4_*`` functions are the three layers for MXFP4: e2m1 nibbles, two
+per byte, ``uint8[17*nblk]`` (``mx4_nbytes``): half the link bytes of the
+8-bit wires at about four times the error of MXFP8.  ``wire_nbytes(name,
+numel)`` sizes a buffer of any wire; a forwarding node on this wire runs the
+combine and the pack as two steps.
 """
 from __future__ import annotations
 
@@ -43,6 +49,10 @@ def mx8_nbytes(numel: int) -> int:
     return 33 * ((int(numel) + MX_BLOCK - 1) // MX_BLOCK)
 
 
+def mx4_nbytes(numel: int) -> int:
+    return 17 * ((int(numel) + MX_BLOCK - 1) // MX_BLOCK)
+
+
 def _numel(shape: Sequence[int]) -> int:
     n = 1
     for d in shape:
@@ -50,7 +60,7 @@ def _numel(shape: Sequence[int]) -> int:
     return n
 
 
-def _blocks(t: torch.Tensor, op: str):
+def _blocks(t: torch.Tensor, op: str, block_bytes: int = 33):
     """``t`` as fp32 blocks ``[nblk, 32]`` (the padded tail is 0.0), the raw
     bits of each block's amax over its finite elements (for |x| the integer
     order is the float order), and the empty wire buffer."""
@@ -59,7 +69,7 @@ def _blocks(t: torch.Tensor, op: str):
     x = t.detach().reshape(-1).to(torch.float32)
     n = x.numel()
     nblk = (n + MX_BLOCK - 1) // MX_BLOCK
-    out = torch.empty(33 * nblk, dtype=torch.uint8, device=x.device)
+    out = torch.empty(block_bytes * nblk, dtype=torch.uint8, device=x.device)
     if nblk * MX_BLOCK != n:
         x = torch.cat([x, x.new_zeros(nblk * MX_BLOCK - n)])
     x = x.view(nblk, MX_BLOCK)
@@ -164,6 +174,61 @@ def mxi8_unpack_torch(buf: torch.Tensor, shape: Union[int, Sequence[int]],
     return x.reshape(-1)[:n].to(dtype).reshape(shape)
 
 
+def mx4_pack_torch(t: torch.Tensor) -> torch.Tensor:
+    """Encode ``t`` (f32/bf16/f16, any device) as MXFP4 with torch ops only."""
+    x, amax, out = _blocks(t, "mx4_pack", 17)
+    nblk = x.shape[0]
+    if nblk == 0:
+        return out
+    nan = ((x.view(torch.int32) & 0x7FFFFFFF) > 0x7F800000).any(dim=1)
+    # smallest 2^(b-127) with amax / 2^(b-127) <= 6 = 1.5 * 2^2: E - 2, one
+    # more from m = 0x400001 on (the add carries into the exponent then)
+    b = (((amax + 0x3FFFFF) >> 23) - 2).clamp_(min=0)
+    v = x * ((254 - b) << 23).view(torch.float32)[:, None]  # exact, or -> 0
+    # e2m1 code of |v| on its bits, clamped to 6.0 (moves +-Inf only).  From
+    # 1.0 on the code is exponent and top mantissa bit, rounded to nearest
+    # even on the 22 bits below (a carry walks into the exponent); below,
+    # 0 up to 0.25, 0.5 up to under 0.75, 1.0 from there.
+    a = (v.view(torch.int32) & 0x7FFFFFFF).clamp(max=0x40C00000)
+    hi = ((a + 0x1FFFFF + ((a >> 22) & 1)) >> 22) - 252
+    lo = (a > 0x3E800000).to(torch.int32) + (a >= 0x3F400000).to(torch.int32)
+    q = torch.where(a >= 0x3F800000, hi, lo) | ((x.view(torch.int32) >> 28) & 8)
+    q = torch.where(nan[:, None], torch.zeros_like(q), q).to(torch.uint8)
+    out[: 16 * nblk] = (q[:, 0::2] | (q[:, 1::2] << 4)).reshape(-1)
+    out[16 * nblk:] = torch.where(nan, torch.full_like(b, 0xFF), b).to(torch.uint8)
+    return out
+
+
+def mx4_unpack_torch(buf: torch.Tensor, shape: Union[int, Sequence[int]],
+                     dtype: torch.dtype) -> torch.Tensor:
+    """Decode an MXFP4 wire buffer into a tensor of ``shape``/``dtype``."""
+    if dtype not in _MX_DTYPES:
+        raise ValueError(f"mx4_unpack: dtype must be f32/bf16/f16, got {dtype}")
+    shape = (int(shape),) if isinstance(shape, int) else tuple(shape)
+    n = _numel(shape)
+    nblk = (n + MX_BLOCK - 1) // MX_BLOCK
+    if buf.dtype != torch.uint8 or buf.numel() != 17 * nblk:
+        raise ValueError(
+            f"mx4_unpack: buffer must be uint8[{17 * nblk}] for {n} elements, "
+            f"got {buf.dtype}[{buf.numel()}]"
+        )
+    if n == 0:
+        return torch.empty(shape, dtype=dtype, device=buf.device)
+    buf = buf.reshape(-1)
+    p = buf[: 16 * nblk].to(torch.int32)
+    q = torch.stack([p & 0xF, p >> 4], dim=1).view(nblk, MX_BLOCK)
+    b = buf[16 * nblk:].to(torch.int32)[:, None]
+    # |e2m1| as fp32 bits: codes 2..7 are exponent c>>1 (bias 1) and mantissa
+    # bit c&1; code 1 is the subnormal 0.5
+    c = q & 7
+    mag = torch.where(c >= 2, (((c >> 1) + 126) << 23) | ((c & 1) << 22), c * 0x3F000000)
+    mult = torch.where(b > 0, b << 23, torch.full_like(b, 0x00400000))
+    x = mag.to(torch.int32).view(torch.float32) * mult.to(torch.int32).view(torch.float32)
+    bits = x.view(torch.int32) | ((q & 8) << 28)  # the sign, of a zero too
+    bits = torch.where(b == 0xFF, torch.full_like(bits, 0x7FC00000), bits)
+    return bits.view(torch.float32).reshape(-1)[:n].to(dtype).reshape(shape)
+
+
 def _f32(v: float) -> float:
     # the kernel takes alpha/beta as C floats
     return float(torch.tensor(float(v), dtype=torch.float32))
@@ -190,6 +255,14 @@ def mxi8_axpby_torch(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
                      out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """:func:`mx8_axpby_torch` for an MXINT8 ``wire``."""
     return _axpby_torch("mxi8_axpby", mxi8_unpack_torch, a, wire, alpha, beta,
+                        out_dtype)
+
+
+def mx4_axpby_torch(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
+                    beta: float = 1.0,
+                    out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """:func:`mx8_axpby_torch` for an MXFP4 ``wire``."""
+    return _axpby_torch("mx4_axpby", mx4_unpack_torch, a, wire, alpha, beta,
                         out_dtype)
 
 
@@ -284,6 +357,22 @@ def mxi8_axpby(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
     return _axpby("mxi8_axpby", mxi8_axpby_torch, a, wire, alpha, beta, dst)
 
 
+def mx4_pack(t: torch.Tensor) -> torch.Tensor:
+    return _pack("mx4_pack", mx4_pack_torch, t)
+
+
+def mx4_unpack(buf: torch.Tensor, shape: Union[int, Sequence[int]],
+               dtype: torch.dtype) -> torch.Tensor:
+    return _unpack("mx4_unpack", mx4_unpack_torch, buf, shape, dtype)
+
+
+def mx4_axpby(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
+              beta: float = 1.0,
+              dst: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`mx8_axpby` for an MXFP4 ``wire``."""
+    return _axpby("mx4_axpby", mx4_axpby_torch, a, wire, alpha, beta, dst)
+
+
 def _axpby_pack(op: str, combine_torch: Callable, pack_torch: Callable, a, second,
                 alpha, beta, dst, wire_out):
     """The step of a forwarding merge-tree node: ``(dst, pack(dst))``.  One
@@ -349,17 +438,52 @@ def mxi8_axpby2_pack(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
                        alpha, beta, dst, wire_out)
 
 
+def _then_pack(dst: torch.Tensor, wire_out: Optional[torch.Tensor]):
+    packed = mx4_pack(dst)
+    if wire_out is None:
+        return dst, packed
+    wire_out.copy_(packed)
+    return dst, wire_out
+
+
+def mx4_axpby_pack(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
+                   beta: float = 1.0, dst: Optional[torch.Tensor] = None,
+                   wire_out: Optional[torch.Tensor] = None):
+    """:func:`mx8_axpby_pack` for MXFP4 buffers, as its two steps:
+    :func:`mx4_axpby`, then :func:`mx4_pack` of ``dst`` (no fused kernel)."""
+    return _then_pack(mx4_axpby(a, wire, alpha, beta, dst), wire_out)
+
+
+def mx4_axpby2_pack(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
+                    beta: float = 1.0, dst: Optional[torch.Tensor] = None,
+                    wire_out: Optional[torch.Tensor] = None):
+    """:func:`mx8_axpby2_pack` with an MXFP4 ``wire_out``, as its two steps:
+    the plain combine (``ops.axpby`` for device tensors), then the pack."""
+    if _native(a):
+        from lzy_amd import ops
+
+        return _then_pack(ops.axpby(a, b, alpha, beta, dst=dst), wire_out)
+    r = _axpby2_torch(a, b, alpha, beta, a.dtype if dst is None else dst.dtype)
+    if dst is None:
+        return _then_pack(r, wire_out)
+    dst.copy_(r)
+    return _then_pack(dst, wire_out)
+
+
 # wire name (channel_wire_cast, stream_wire_cast, a plan's "wire") -> the
-# dispatching (pack, unpack, axpby); both codecs share mx8_nbytes
+# dispatching (pack, unpack, axpby), and the size of its buffer
 _WIRE_CODECS = {
     "mxfp8": (mx8_pack, mx8_unpack, mx8_axpby),
     "mxint8": (mxi8_pack, mxi8_unpack, mxi8_axpby),
+    "mxfp4": (mx4_pack, mx4_unpack, mx4_axpby),
 }
+_WIRE_NBYTES = {"mxfp8": mx8_nbytes, "mxint8": mx8_nbytes, "mxfp4": mx4_nbytes}
 MX_WIRES = tuple(_WIRE_CODECS)
 # ... -> the dispatching (axpby_pack, axpby2_pack) of a forwarding node
 _WIRE_FUSED = {
     "mxfp8": (mx8_axpby_pack, mx8_axpby2_pack),
     "mxint8": (mxi8_axpby_pack, mxi8_axpby2_pack),
+    "mxfp4": (mx4_axpby_pack, mx4_axpby2_pack),
 }
 
 
@@ -367,6 +491,13 @@ def wire_codec(wire: str) -> Tuple[Callable, Callable, Callable]:
     if wire not in _WIRE_CODECS:
         raise ValueError(f"wire must be one of {MX_WIRES}, got {wire!r}")
     return _WIRE_CODECS[wire]
+
+
+def wire_nbytes(wire: str, numel: int) -> int:
+    """Bytes of the wire buffer that carries ``numel`` elements on ``wire``."""
+    if wire not in _WIRE_NBYTES:
+        raise ValueError(f"wire must be one of {MX_WIRES}, got {wire!r}")
+    return _WIRE_NBYTES[wire](numel)
 
 
 def wire_fused(wire: str) -> Tuple[Callable, Callable]:

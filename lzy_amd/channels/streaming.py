@@ -37,10 +37,11 @@ def streamed_reduce_pair(
     its ``t`` in chunks and returns None.  Both sides must pass the same
     shape/dtype/chunk_bytes and the same ``wire``.
 
-    ``wire="mxfp8"`` or ``"mxint8"`` (f32/bf16/f16 only): chunks are a
+    ``wire="mxfp8"``, ``"mxint8"`` or ``"mxfp4"`` (f32/bf16/f16 only): chunks are a
     multiple of 256 elements and cross the link as self-contained buffers
     of that codec (docs/mxwire.md); the sender packs each one, the receiver
-    combines with the codec's fused decode (``mx8_axpby``, ``mxi8_axpby``).
+    combines with the codec's fused decode (``mx8_axpby``, ``mxi8_axpby``,
+    ``mx4_axpby``).
     Device tensors on a gloo group are staged through the host as packed
     bytes: packed by the kernel before, combined by the kernel after.
     """
@@ -130,7 +131,7 @@ def _streamed_reduce_pair_mx(t, flat, peer, is_receiver, alpha, beta, per, group
 
     out = torch.empty_like(flat)
     bufs = [
-        torch.empty(mxwire.mx8_nbytes(min(per, n)), dtype=torch.uint8,
+        torch.empty(mxwire.wire_nbytes(wire, min(per, n)), dtype=torch.uint8,
                     device=None if host_stage else flat.device,
                     pin_memory=host_stage)
         for _ in range(2)
@@ -139,7 +140,7 @@ def _streamed_reduce_pair_mx(t, flat, peer, is_receiver, alpha, beta, per, group
     def post(i: int):
         s = starts[i]
         ln = min(s + per, n) - s
-        wb = bufs[i % 2][: mxwire.mx8_nbytes(ln)]
+        wb = bufs[i % 2][: mxwire.wire_nbytes(wire, ln)]
         return dist.irecv(wb, src=peer, group=group), s, ln, wb
 
     inflight = post(0) if starts else None

@@ -212,14 +212,14 @@ def _should_wirecast(dtype: torch.dtype, numel: int, wire) -> bool:
     )
 
 
-# "mxfp8" and "mxint8" are not torch dtypes: the block-scaled 8-bit codecs
+# "mxfp8", "mxint8" and "mxfp4" are not torch dtypes: the block-scaled codecs
 # (channels/mxwire.py) pack into a flat uint8 buffer, which every path
 # carries — RCCL device, the host-staged fallback and CPU tensors over gloo.
 
 
 def wire_cast_mx() -> str:
     """The block-scaled codec ``channel_wire_cast`` names ("mxfp8",
-    "mxint8"), or "" when it names none."""
+    "mxint8", "mxfp4"), or "" when it names none."""
     from lzy_amd.channels.mxwire import MX_WIRES
     from lzy_amd.config import get_config
 
@@ -491,7 +491,7 @@ class Transport:
                 from lzy_amd.channels import mxwire
 
                 wire_dtype = torch.uint8
-                wire_shape: Tuple[int, ...] = (mxwire.mx8_nbytes(numel),)
+                wire_shape: Tuple[int, ...] = (mxwire.wire_nbytes(self._mx, numel),)
             else:
                 wire_shape = meta.shape
             per = self._chunk_elems(

@@ -29,11 +29,12 @@ the driver keeps at most one plan active pool-wide, and per (src, dst)
 pair every rank issues chunk-major in global topo order — pairwise
 consistent by construction (checked at build time).
 
-Wire format: with ``build_plan(..., wire="mxfp8")`` or ``"mxint8"`` (driver
-config ``stream_wire_cast``) the remote edges of an f32/bf16/f16 plan cross
-the link as block-scaled 8-bit chunks — each chunk a self-contained MXFP8
-or MXINT8 buffer, packed by the sender and combined by the codec's fused
-decode (``mxwire.mx8_axpby``, ``mxwire.mxi8_axpby``) on arrival
+Wire format: with ``build_plan(..., wire="mxfp8")``, ``"mxint8"`` or
+``"mxfp4"`` (driver config ``stream_wire_cast``) the remote edges of an
+f32/bf16/f16 plan cross the link as block-scaled chunks — each chunk a
+self-contained buffer of that codec (``mxwire.wire_nbytes``), packed by the
+sender and combined by the codec's fused decode (``mxwire.mx8_axpby``,
+``mxwire.mxi8_axpby``, ``mxwire.mx4_axpby``) on arrival
 (docs/mxwire.md, "Plans").  The decision travels in the plan; ranks never
 consult their own configuration.
 """
@@ -51,7 +52,7 @@ from lzy_amd.utils.metrics import METRICS
 
 _LOG = logging.getLogger("lzy_amd.treeplan")
 
-WIRE_MODES = ("", "mxfp8", "mxint8")
+WIRE_MODES = ("", "mxfp8", "mxint8", "mxfp4")
 _WIRE_DTYPES = ("float32", "bfloat16", "float16")
 WIRE_MIN_NUMEL = 65536      # the transport's wire-cast threshold
 WIRE_CHUNK_QUANTUM = 256    # elements; chunk_elems of a wired plan
@@ -155,8 +156,8 @@ def build_plan(
     order inconsistency) — the caller then falls back to op-by-op
     execution.
 
-    ``wire="mxfp8"`` / ``"mxint8"`` asks for that block-scaled 8-bit wire
-    (docs/mxwire.md) on the plan's remote edges.  The driver alone decides: the plan carries
+    ``wire="mxfp8"`` / ``"mxint8"`` / ``"mxfp4"`` asks for that block-scaled
+    wire (docs/mxwire.md) on the plan's remote edges.  The driver alone decides: the plan carries
     the outcome in ``plan["wire"]`` and ranks follow it, never their own
     configuration.  Plans of another dtype or under the transport's size
     threshold stay exact (``"wire": ""``).
@@ -353,7 +354,7 @@ def run_stream_plan(
         wire_pack, _, wire_axpby = mxwire.wire_codec(plan["wire"])
         # a node that forwards combines and re-encodes in one step
         wire_axpby_pack, wire_axpby2_pack = mxwire.wire_fused(plan["wire"])
-        wper = mxwire.mx8_nbytes(per)  # chunk j starts at byte j * wper
+        wper = mxwire.wire_nbytes(plan["wire"], per)  # chunk j starts at byte j * wper
 
     def flat_entry(eid: str) -> torch.Tensor:
         if not store.has(eid) and not store.wait_present(eid, timeout=wait_timeout):
@@ -418,8 +419,8 @@ def run_stream_plan(
                 seq_by_src.setdefault(st["remote_src"], []).append(st)
         recv_buf: Dict[int, torch.Tensor] = {}  # step topo -> full buffer
         if wired:
-            recv_len = (nchunks - 1) * wper + mxwire.mx8_nbytes(
-                numel - (nchunks - 1) * per
+            recv_len = (nchunks - 1) * wper + mxwire.wire_nbytes(
+                plan["wire"], numel - (nchunks - 1) * per
             )
         for src, sts in seq_by_src.items():
             for st in sts:
@@ -441,7 +442,7 @@ def run_stream_plan(
             s, e = chunk_bounds(j)
             if not wired:
                 return s, e
-            return j * wper, j * wper + mxwire.mx8_nbytes(e - s)
+            return j * wper, j * wper + mxwire.wire_nbytes(plan["wire"], e - s)
 
         nonce = plan.get("nonce", 0)
 

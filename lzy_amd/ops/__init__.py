@@ -27,6 +27,7 @@ _MXI8 = False  # ... and lz_mxi8_pack / lz_mxi8_unpack / lz_mxi8_axpby (MXINT8)
 # ... and lz_mx8_axpby_pack / lz_mx8_axpby2_pack and their mxi8 twins (the
 # fused combine + re-encode of a forwarding merge-tree node)
 _MX_AXPBY_PACK = False
+_MX4 = False  # ... and lz_mx4_pack / lz_mx4_unpack / lz_mx4_axpby (MXFP4)
 _SEGCOPY = False  # ... and lz_segcopy (the packed-bundle gather/scatter)
 # bytes per tile of the segmented copy — LZ_SEG_TILE in hipops.hip
 SEGCOPY_TILE = 16384
@@ -188,6 +189,17 @@ def _try_load() -> Optional[ctypes.CDLL]:
         _MX_AXPBY_PACK = True
     except AttributeError:
         _MX_AXPBY_PACK = False
+    global _MX4
+    try:
+        lib.lz_mx4_pack.restype = ctypes.c_int
+        lib.lz_mx4_pack.argtypes = lib.lz_mx8_pack.argtypes
+        lib.lz_mx4_unpack.restype = ctypes.c_int
+        lib.lz_mx4_unpack.argtypes = lib.lz_mx8_unpack.argtypes
+        lib.lz_mx4_axpby.restype = ctypes.c_int
+        lib.lz_mx4_axpby.argtypes = lib.lz_mx8_axpby.argtypes
+        _MX4 = True
+    except AttributeError:
+        _MX4 = False
     global _SEGCOPY
     try:
         lib.lz_segcopy.restype = ctypes.c_int
@@ -335,6 +347,8 @@ def _mx_entry(op: str):
     lib = _require_native()
     if op.endswith("_pack") and "axpby" in op:
         present = _MX_AXPBY_PACK
+    elif op.startswith("mx4_"):
+        present = _MX4
     else:
         present = _MX8_AXPBY if op == "mx8_axpby" else _MXI8
     if not present:
@@ -350,6 +364,16 @@ def mx8_nbytes(numel: int) -> int:
     (MXFP8 and MXINT8 alike): 32 payload bytes + 1 scale byte per
     32-element block."""
     return 33 * ((int(numel) + 31) // 32)
+
+
+def mx4_nbytes(numel: int) -> int:
+    """Wire bytes of ``numel`` elements in the block-scaled 4-bit format
+    (MXFP4): 16 payload bytes + 1 scale byte per 32-element block."""
+    return 17 * ((int(numel) + 31) // 32)
+
+
+def _mx_nbytes(op: str, numel: int) -> int:
+    return mx4_nbytes(numel) if op.startswith("mx4_") else mx8_nbytes(numel)
 
 
 def _mx8_check_dtype(dtype, what: str) -> None:
@@ -373,6 +397,12 @@ def mxi8_pack(t, out=None):
     return _mx_pack("mxi8_pack", t, out)
 
 
+def mx4_pack(t, out=None):
+    """:func:`mx8_pack` for the block-scaled FP4 (MXFP4) wire format
+    (docs/mxwire.md): e2m1 nibbles, ``mx4_nbytes(t.numel())`` bytes."""
+    return _mx_pack("mx4_pack", t, out)
+
+
 def _mx_pack(op: str, t, out):
     import torch
 
@@ -382,7 +412,7 @@ def _mx_pack(op: str, t, out):
     fn = _mx_entry(op)
     s = t.detach().contiguous()
     n = s.numel()
-    nbytes = mx8_nbytes(n)
+    nbytes = _mx_nbytes(op, n)
     if out is None:
         out = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
     elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
@@ -413,6 +443,12 @@ def mxi8_unpack(buf, numel_or_shape, dtype, out=None):
     return _mx_unpack("mxi8_unpack", buf, numel_or_shape, dtype, out)
 
 
+def mx4_unpack(buf, numel_or_shape, dtype, out=None):
+    """:func:`mx8_unpack` for an MXFP4 wire buffer
+    (``uint8[mx4_nbytes(numel)]``)."""
+    return _mx_unpack("mx4_unpack", buf, numel_or_shape, dtype, out)
+
+
 def _mx_unpack(op: str, buf, numel_or_shape, dtype, out):
     import torch
 
@@ -427,9 +463,9 @@ def _mx_unpack(op: str, buf, numel_or_shape, dtype, out):
         raise ValueError(f"{op} requires a device buffer")
     _mx8_check_dtype(dtype, op)
     if buf.dtype != torch.uint8 or not buf.is_contiguous() \
-            or buf.numel() != mx8_nbytes(n):
+            or buf.numel() != _mx_nbytes(op, n):
         raise ValueError(
-            f"{op}: buffer must be contiguous uint8[{mx8_nbytes(n)}] "
+            f"{op}: buffer must be contiguous uint8[{_mx_nbytes(op, n)}] "
             f"for {n} elements, got {buf.dtype}[{buf.numel()}]"
         )
     fn = _mx_entry(op)
@@ -471,6 +507,13 @@ def mxi8_axpby(a, wire, alpha: float = 1.0, beta: float = 1.0, dst=None):
     return _mx_axpby("mxi8_axpby", a, wire, alpha, beta, dst)
 
 
+def mx4_axpby(a, wire, alpha: float = 1.0, beta: float = 1.0, dst=None):
+    """:func:`mx8_axpby` with the MXFP4 decode fused in: ``wire`` is an
+    MXFP4 buffer (``uint8[mx4_nbytes(a.numel())]``), everything else is the
+    same."""
+    return _mx_axpby("mx4_axpby", a, wire, alpha, beta, dst)
+
+
 def _mx_axpby(op: str, a, wire, alpha, beta, dst):
     import torch
 
@@ -479,9 +522,9 @@ def _mx_axpby(op: str, a, wire, alpha, beta, dst):
     _mx8_check_dtype(a.dtype, op)
     n = a.numel()
     if wire.dtype != torch.uint8 or not wire.is_contiguous() \
-            or wire.numel() != mx8_nbytes(n):
+            or wire.numel() != _mx_nbytes(op, n):
         raise ValueError(
-            f"{op}: wire must be contiguous uint8[{mx8_nbytes(n)}] "
+            f"{op}: wire must be contiguous uint8[{_mx_nbytes(op, n)}] "
             f"for {n} elements, got {wire.dtype}[{wire.numel()}]"
         )
     if dst is not None:

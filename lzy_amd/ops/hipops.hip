@@ -1445,6 +1445,358 @@ extern "C" hipError_t lz_mxi8_axpby(const void* a, int a_dtype, const void* wire
 }
 
 // ---------------------------------------------------------------------------
+// mx4: the block-scaled FP4 codec (OCP MXFP4, docs/mxwire.md "MXFP4").
+//
+// Every 32 elements share one E8M0 scale byte; an element is an e2m1 nibble
+// (sign, codes 0..7 = 0, .5, 1, 1.5, 2, 3, 4, 6), two per byte, low nibble
+// first.  Wire buffer for n elements, nblk = ceil(n/32): payload bytes
+// [0, 16*nblk), then nblk scale bytes: 17/32 B per element.  A block with a
+// NaN is scale byte 0xff over an all-zero payload.
+//
+// Work item = 8 consecutive elements, which are exactly one payload dword:
+// the 4 lanes of an aligned quad own one block (16 contiguous payload
+// bytes), a wave 16 blocks (256 contiguous payload bytes, 16 scale bytes).
+// The converts are gfx950's v_cvt_scalef32_pk_fp4_f32 / _pk_f32_fp4 with
+// the block's scale as their E8M0 operand (the exponent field of the float
+// b << 23; b == 0 is read as 2^-127): two elements per instruction, no
+// separate scaling multiply.  On this hardware they round ties to even,
+// keep the sign of a zero result, saturate +-Inf and anything beyond 6 to
+// +-6, and decode every nibble under scale 0xff to NaN, which is the format.
+// They turn a NaN *element* into +-6, which is not: the pack therefore finds
+// NaN in the amax pass and overrides the whole block.
+//
+// ALIGNED: 16 B accesses to the tensors and 4 B accesses to the wire.
+// Element-aligned views and the tail take the guarded path of the same
+// kernel.  Compiled without packed fp32 VALU ops, as the mxi8 kernels are.
+// ---------------------------------------------------------------------------
+
+// scale byte of a block from the raw bits of its finite amax (>= 0): the
+// smallest 2^(b-127) with amax / 2^(b-127) <= 6 = 1.5 * 2^2, i.e. E - 2, one
+// more from m = 0x400001 on (adding 0x3fffff carries into the exponent
+// exactly then), not below 0.  FLT_MAX gives 253.
+__device__ __forceinline__ uint32_t lz_mx4_scale_byte(uint32_t amax_bits) {
+    const uint32_t t = (amax_bits + 0x3fffffu) >> 23;
+    return t > 2u ? t - 2u : 0u;
+}
+
+// quantize and store one group (8 elements of lane `lane`, group g); every
+// lane of the wave calls this together (DPP).  FULL: all 64 groups of the
+// wave are inside the tensor.
+template <bool ALIGNED, bool FULL>
+__device__ __forceinline__ void lz_mx4_emit(const float (&f)[8], int64_t g, int lane,
+                                            int64_t ngroups, int64_t nblk,
+                                            uint8_t* __restrict__ dst,
+                                            uint8_t* __restrict__ scales) {
+    // one pass over raw |x| bits: the finite amax (biased by one exponent
+    // step so that Inf/NaN wrap negative and lose the signed max) and the
+    // plain unsigned max, which exceeds Inf's bits iff the lane holds a NaN
+    int32_t tmax = 0x00800000;
+    uint32_t umax = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t a = __float_as_uint(f[k]) & 0x7fffffffu;
+        const int32_t t = (int32_t)(a + 0x00800000u);
+        umax = a > umax ? a : umax;
+        tmax = t > tmax ? t : tmax;
+    }
+    // both travel the quad reduce as one key: a NaN lane sends all ones,
+    // above every finite amax, so the has-NaN flag costs no DPP step
+    uint32_t key = umax > 0x7f800000u ? 0xffffffffu : (uint32_t)tmax - 0x00800000u;
+    uint32_t o = lz_dpp<LZ_DPP_QUAD_XOR1>(key);
+    key = o > key ? o : key;
+    o = lz_dpp<LZ_DPP_QUAD_XOR2>(key);
+    key = o > key ? o : key;
+    const bool nan = key > 0x7f7fffffu;
+    const uint32_t b = nan ? 0xffu : lz_mx4_scale_byte(key);
+
+    // element 2i -> low nibble of byte i, 2i+1 -> high nibble; the immediate
+    // picks the byte of the dword, the other bytes pass through
+    const float scale = __uint_as_float(b << 23);
+    uint32_t w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(0u, f[0], f[1], scale, 0);
+    w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[2], f[3], scale, 1);
+    w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[4], f[5], scale, 2);
+    w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, f[6], f[7], scale, 3);
+    w = nan ? 0u : w;
+
+    // the 4 scale bytes of each 16-lane row, gathered into its first lane
+    uint32_t sw = b;
+    sw |= lz_dpp<LZ_DPP_ROW_SHL(4)>(b) << 8;
+    sw |= lz_dpp<LZ_DPP_ROW_SHL(8)>(b) << 16;
+    sw |= lz_dpp<LZ_DPP_ROW_SHL(12)>(b) << 24;
+
+    if (FULL || g < ngroups) {
+        if (ALIGNED) {
+            *reinterpret_cast<uint32_t*>(dst + g * 4) = w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dst[g * 4 + k] = (uint8_t)(w >> (8 * k));
+        }
+        if ((lane & 15) == 0) {
+            const int64_t blk = g >> 2;  // multiple of 4
+            if (ALIGNED && (FULL || blk + 4 <= nblk)) {
+                *reinterpret_cast<uint32_t*>(scales + blk) = sw;
+            } else {
+                for (int k = 0; k < 4 && blk + k < nblk; ++k)
+                    scales[blk + k] = (uint8_t)(sw >> (8 * k));
+            }
+        }
+    }
+}
+
+// The loop of lz_mx_pack_body: wave-uniform bounds, two groups per trip, so
+// that on the unguarded path both 16 B loads issue before either is consumed.
+template <typename T, bool ALIGNED>
+__global__ void __launch_bounds__(LZ_BLOCK) LZ_NO_PK_F32
+mx4_pack_kernel(const T* __restrict__ src, uint8_t* __restrict__ dst, int64_t n) {
+    const int64_t nblk = (n + 31) >> 5;
+    const int64_t ngroups = nblk * 4;
+    uint8_t* __restrict__ scales = dst + nblk * 16;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+
+    for (int64_t g0 = (int64_t)blockIdx.x * blockDim.x + wave * 64; g0 < ngroups;
+         g0 += 2 * stride) {
+        const int64_t ga = g0 + lane, gb = ga + stride;
+        float fa[8], fb[8];
+        if (ALIGNED && (g0 + stride + 64) * 8 <= n) {
+            lz_mx8_load<T, true>(src, ga * 8, n, fa);
+            lz_mx8_load<T, true>(src, gb * 8, n, fb);
+            lz_mx4_emit<true, true>(fa, ga, lane, ngroups, nblk, dst, scales);
+            lz_mx4_emit<true, true>(fb, gb, lane, ngroups, nblk, dst, scales);
+        } else {
+            const bool two = g0 + stride < ngroups;  // wave-uniform
+            lz_mx8_load<T, false>(src, ga * 8, n, fa);
+            lz_mx4_emit<ALIGNED, false>(fa, ga, lane, ngroups, nblk, dst, scales);
+            if (two) {
+                lz_mx8_load<T, false>(src, gb * 8, n, fb);
+                lz_mx4_emit<ALIGNED, false>(fb, gb, lane, ngroups, nblk, dst, scales);
+            }
+        }
+    }
+}
+
+// the payload dword of group g (it exists for every g < 4*nblk)
+template <bool ALIGNED>
+__device__ __forceinline__ uint32_t lz_mx4_payload(const uint8_t* __restrict__ wire,
+                                                   int64_t g) {
+    if (ALIGNED) return *reinterpret_cast<const uint32_t*>(wire + g * 4);
+    uint32_t w = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w |= (uint32_t)wire[g * 4 + k] << (8 * k);
+    return w;
+}
+
+// decode one group and store it, or (COMBINE) its combine with the 8
+// elements fa of the accumulator: fmaf(a, alpha, x * beta), x in fp32.
+// FULL: all 8 elements lie in [0, n) and dst + e0 is 16 B-aligned.
+template <typename DstT, bool FULL, bool COMBINE>
+__device__ __forceinline__ void lz_mx4_dec_store(uint32_t w, uint32_t b,
+                                                 const float (&fa)[8], DstT* dst,
+                                                 int64_t e0, int64_t n, float alpha,
+                                                 float beta) {
+    constexpr int V = 8;
+    const float scale = __uint_as_float(b << 23);
+    const lz_f32x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 0);
+    const lz_f32x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 1);
+    const lz_f32x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 2);
+    const lz_f32x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, scale, 3);
+    const float x[V] = {p0.x, p0.y, p1.x, p1.y, p2.x, p2.y, p3.x, p3.y};
+    DstT y[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        float r = x[k];
+        if constexpr (COMBINE) {
+            r = fmaf(fa[k], alpha, x[k] * beta);
+            // the contract rounds to fp32, then to the 16-bit type: keep the
+            // FMA and the f16 convert from fusing into one single-rounding
+            // v_fma_mixlo_f16
+#if defined(__HIP_DEVICE_COMPILE__)
+            if constexpr (std::is_same<DstT, __half>::value) asm("" : "+v"(r));
+#endif
+        }
+        y[k] = lz_from_float<DstT>(r);
+    }
+    if (FULL) {
+        LzVec16 q[sizeof(DstT) * V / 16];
+        __builtin_memcpy(q, y, sizeof(y));
+        LzVec16* p = reinterpret_cast<LzVec16*>(dst + e0);
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(DstT) * V / 16); ++k) p[k] = q[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            if (e0 + k < n) dst[e0 + k] = y[k];
+    }
+}
+
+// one group on the guarded path (the tail, and element-aligned views)
+template <typename SrcT, typename DstT, bool ALIGNED, bool COMBINE>
+__device__ __forceinline__ void lz_mx4_dec_one(const SrcT* a,
+                                               const uint8_t* __restrict__ wire,
+                                               const uint8_t* __restrict__ scales,
+                                               DstT* dst, int64_t g, int64_t n,
+                                               float alpha, float beta) {
+    const int64_t e0 = g * 8;
+    if (e0 >= n) return;  // padded tail of the last block
+    const uint32_t w = lz_mx4_payload<ALIGNED>(wire, g);
+    const uint32_t b = scales[g >> 2];
+    float fa[8] = {};
+    if (ALIGNED && e0 + 8 <= n) {
+        if constexpr (COMBINE) lz_mx8_load<SrcT, true>(a, e0, n, fa);
+        lz_mx4_dec_store<DstT, true, COMBINE>(w, b, fa, dst, e0, n, alpha, beta);
+    } else {
+        if constexpr (COMBINE) lz_mx8_load<SrcT, false>(a, e0, n, fa);
+        lz_mx4_dec_store<DstT, false, COMBINE>(w, b, fa, dst, e0, n, alpha, beta);
+    }
+}
+
+// mx4_unpack (COMBINE false: a unused) and mx4_axpby share this kernel: one
+// payload dword and the block's scale byte per lane, 8 elements out, nothing
+// crosses lanes.  Two groups per grid-stride trip, every load of both issued
+// before the first store.  `a` and `dst` may be the same pointer (a lane
+// reads its 8 elements before it writes them), so neither is __restrict__.
+template <typename SrcT, typename DstT, bool ALIGNED, bool COMBINE>
+__global__ void __launch_bounds__(LZ_BLOCK) LZ_NO_PK_F32
+mx4_decode_kernel(const SrcT* a, const uint8_t* __restrict__ wire, DstT* dst, int64_t n,
+                  float alpha, float beta) {
+    const int64_t nblk = (n + 31) >> 5;
+    const int64_t ngroups = nblk * 4;
+    const uint8_t* __restrict__ scales = wire + nblk * 16;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+
+    for (int64_t ga = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ga < ngroups;
+         ga += 2 * stride) {
+        const int64_t gb = ga + stride;
+        if (ALIGNED && (gb + 1) * 8 <= n) {  // ga < gb: both groups whole
+            const uint32_t wa = lz_mx4_payload<true>(wire, ga);
+            const uint32_t wb = lz_mx4_payload<true>(wire, gb);
+            const uint32_t ba = scales[ga >> 2], bb = scales[gb >> 2];
+            float fa[8] = {}, fb[8] = {};
+            if constexpr (COMBINE) {
+                lz_mx8_load<SrcT, true>(a, ga * 8, n, fa);
+                lz_mx8_load<SrcT, true>(a, gb * 8, n, fb);
+            }
+            lz_mx4_dec_store<DstT, true, COMBINE>(wa, ba, fa, dst, ga * 8, n, alpha, beta);
+            lz_mx4_dec_store<DstT, true, COMBINE>(wb, bb, fb, dst, gb * 8, n, alpha, beta);
+        } else {
+            lz_mx4_dec_one<SrcT, DstT, ALIGNED, COMBINE>(a, wire, scales, dst, ga, n, alpha,
+                                                         beta);
+            if (gb < ngroups)
+                lz_mx4_dec_one<SrcT, DstT, ALIGNED, COMBINE>(a, wire, scales, dst, gb, n,
+                                                             alpha, beta);
+        }
+    }
+}
+
+static inline bool lz_mx_float_dtype(int d) {
+    return d == LZ_F32 || d == LZ_F16 || d == LZ_BF16;
+}
+
+// src: n elements of src_dtype (f32/f16/bf16); dst_u8: 17*ceil(n/32) bytes
+extern "C" hipError_t lz_mx4_pack(const void* src, int src_dtype, void* dst_u8,
+                                  int64_t n, void* stream) {
+    if (!lz_mx_float_dtype(src_dtype) || n < 0) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    const int blocks = lz_mx8_grid(n);
+    const bool aligned = (((uintptr_t)src & 15) == 0) && (((uintptr_t)dst_u8 & 3) == 0);
+#define LZ_MX4P_CASE(code, T)                                                   \
+    case code:                                                                  \
+        if (aligned)                                                            \
+            hipLaunchKernelGGL((mx4_pack_kernel<T, true>), dim3(blocks),        \
+                               dim3(LZ_BLOCK), 0, s, (const T*)src,             \
+                               (uint8_t*)dst_u8, n);                            \
+        else                                                                    \
+            hipLaunchKernelGGL((mx4_pack_kernel<T, false>), dim3(blocks),       \
+                               dim3(LZ_BLOCK), 0, s, (const T*)src,             \
+                               (uint8_t*)dst_u8, n);                            \
+        break;
+    switch (src_dtype) {
+        LZ_MX4P_CASE(LZ_F32, float)
+        LZ_MX4P_CASE(LZ_F16, __half)
+        LZ_MX4P_CASE(LZ_BF16, __hip_bfloat16)
+        default: return hipErrorInvalidValue;
+    }
+#undef LZ_MX4P_CASE
+    return hipGetLastError();
+}
+
+template <typename SrcT, typename DstT, bool COMBINE>
+static void lz_mx4_decode_launch(const void* a, const void* wire_u8, void* dst, int64_t n,
+                                 float alpha, float beta, bool aligned, hipStream_t s) {
+    const int blocks = lz_mx8_grid(n);
+    if (aligned)
+        hipLaunchKernelGGL((mx4_decode_kernel<SrcT, DstT, true, COMBINE>), dim3(blocks),
+                           dim3(LZ_BLOCK), 0, s, (const SrcT*)a, (const uint8_t*)wire_u8,
+                           (DstT*)dst, n, alpha, beta);
+    else
+        hipLaunchKernelGGL((mx4_decode_kernel<SrcT, DstT, false, COMBINE>), dim3(blocks),
+                           dim3(LZ_BLOCK), 0, s, (const SrcT*)a, (const uint8_t*)wire_u8,
+                           (DstT*)dst, n, alpha, beta);
+}
+
+// src_u8: 17*ceil(n/32) bytes; dst: n elements of dst_dtype (f32/f16/bf16)
+extern "C" hipError_t lz_mx4_unpack(const void* src_u8, void* dst, int dst_dtype,
+                                    int64_t n, void* stream) {
+    if (!lz_mx_float_dtype(dst_dtype) || n < 0) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    const bool aligned = (((uintptr_t)src_u8 & 3) == 0) && (((uintptr_t)dst & 15) == 0);
+    switch (dst_dtype) {
+        case LZ_F32:
+            lz_mx4_decode_launch<float, float, false>(nullptr, src_u8, dst, n, 0.f, 0.f,
+                                                      aligned, s);
+            break;
+        case LZ_F16:
+            lz_mx4_decode_launch<__half, __half, false>(nullptr, src_u8, dst, n, 0.f, 0.f,
+                                                        aligned, s);
+            break;
+        default:
+            lz_mx4_decode_launch<__hip_bfloat16, __hip_bfloat16, false>(
+                nullptr, src_u8, dst, n, 0.f, 0.f, aligned, s);
+            break;
+    }
+    return hipGetLastError();
+}
+
+// a: n elements of a_dtype; wire_u8: 17*ceil(n/32) bytes; dst: n elements of
+// dst_dtype (both f32/f16/bf16).  dst == a is allowed, partial overlap is not.
+extern "C" hipError_t lz_mx4_axpby(const void* a, int a_dtype, const void* wire_u8,
+                                   void* dst, int dst_dtype, int64_t n, float alpha,
+                                   float beta, void* stream) {
+    if (!lz_mx_float_dtype(a_dtype) || !lz_mx_float_dtype(dst_dtype) || n < 0)
+        return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    const bool aligned = (((uintptr_t)a & 15) == 0) && (((uintptr_t)dst & 15) == 0) &&
+                         (((uintptr_t)wire_u8 & 3) == 0);
+#define LZ_MX4A_DST(SrcT, code, DstT)                                           \
+    case code:                                                                  \
+        lz_mx4_decode_launch<SrcT, DstT, true>(a, wire_u8, dst, n, alpha, beta, \
+                                               aligned, s);                     \
+        break;
+#define LZ_MX4A_SRC(scode, SrcT)                                                \
+    case scode:                                                                 \
+        switch (dst_dtype) {                                                    \
+            LZ_MX4A_DST(SrcT, LZ_F32, float)                                    \
+            LZ_MX4A_DST(SrcT, LZ_F16, __half)                                   \
+            default:                                                            \
+                LZ_MX4A_DST(SrcT, LZ_BF16, __hip_bfloat16)                      \
+        }                                                                       \
+        break;
+    switch (a_dtype) {
+        LZ_MX4A_SRC(LZ_F32, float)
+        LZ_MX4A_SRC(LZ_F16, __half)
+        default:
+            LZ_MX4A_SRC(LZ_BF16, __hip_bfloat16)
+    }
+#undef LZ_MX4A_SRC
+#undef LZ_MX4A_DST
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // mx8_axpby_pack / mx8_axpby2_pack: the step of a merge-tree node that
 // forwards (docs/mxwire.md, "Forwarding nodes"), in one pass:
 //   dst      = cast(alpha*a + beta*x)   x = decode(wire_in), or a plain b

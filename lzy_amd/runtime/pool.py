@@ -1214,10 +1214,10 @@ class _DriverScheduler:
         # wire format of streamed plans; the driver decides, the plan
         # carries it to the ranks (channel_wire_cast leaves plans exact)
         self._stream_wire = str(getattr(cfg, "stream_wire_cast", "") or "")
-        if self._stream_wire not in ("", "mxfp8", "mxint8"):
+        if self._stream_wire not in ("", "mxfp8", "mxint8", "mxfp4"):
             raise ValueError(
-                f"stream_wire_cast must be \"\", \"mxfp8\" or \"mxint8\", "
-                f"got {self._stream_wire!r}"
+                f"stream_wire_cast must be \"\", \"mxfp8\", \"mxint8\" or "
+                f"\"mxfp4\", got {self._stream_wire!r}"
             )
         # wire format of tensor bundles (docs/bundles.md): again the
         # driver's decision, carried by the transfer items
@@ -1954,12 +1954,13 @@ class _DriverScheduler:
             for st in sts
         )
         if plan["wire"]:
-            # a wired edge carries one MXFP8 buffer per chunk
-            from lzy_amd.channels.mxwire import mx8_nbytes
+            # a wired edge carries one buffer of the plan's codec per chunk
+            from lzy_amd.channels.mxwire import wire_nbytes
 
             per, numel = plan["chunk_elems"], plan["numel"]
             edge_bytes = sum(
-                mx8_nbytes(min(per, numel - s)) for s in range(0, numel, per)
+                wire_nbytes(plan["wire"], min(per, numel - s))
+                for s in range(0, numel, per)
             )
         else:
             elem = torch.empty(
