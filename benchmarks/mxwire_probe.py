@@ -35,14 +35,18 @@ the two in one process:
 and checks that both give the same values to one unit in the last place.
 
 ``--mode forward`` times the step of a merge-tree node that forwards, for
-both codecs, bf16 and f32, at a plan's chunk size and on a 1 GiB operand:
+every codec (``--forward-codec`` picks one), bf16 and f32, at a plan's chunk
+size and on a 1 GiB operand:
 
   * pair   ops.mx8_axpby(a, wire_in, dst=out); ops.mx8_pack(out, out=wire_out)
                                                         4+33/32 B read, 2+33/32 B written (bf16)
   * fused  ops.mx8_axpby_pack(a, wire_in, dst=out, wire_out=wire_out)
                                                         2+33/32 B read, 2+33/32 B written (bf16)
 
-and checks that both leave the same bytes in ``out`` and ``wire_out``.
+and checks that both leave the same bytes in ``out`` and ``wire_out``.  For
+``mxfp4`` (17/32 B per element on each wire side) it also times the node whose
+two inputs are local: ``ops.axpby`` then ``ops.mx4_pack`` against
+``ops.mx4_axpby2_pack`` (the ``_plain`` keys).
 """
 import argparse
 import ctypes
@@ -146,49 +150,59 @@ def forward_mode(args) -> None:
     at the default stream_chunk_mb) and on a 1 GiB operand."""
     alpha, beta = 0.5, 0.5
     result = {"mode": "forward", "iters": args.iters}
-    for codec in ("mxfp8", "mxint8"):  # the codecs with a fused forwarding kernel
+    codecs = _PREFIX if args.forward_codec == "all" else (args.forward_codec,)
+    for codec in codecs:
         pre = _PREFIX[codec]
-        pack, axpby, axpby_pack = (getattr(ops, f"{pre}_{k}")
-                                   for k in ("pack", "axpby", "axpby_pack"))
+        pack, axpby, axpby_pack, axpby2_pack = (
+            getattr(ops, f"{pre}_{k}") for k in ("pack", "axpby", "axpby_pack", "axpby2_pack"))
+        # the second operand: a received wire chunk, or (mxfp4 only, the
+        # node whose two inputs are local) a plain tensor
         for dtype, name in ((torch.bfloat16, "bf16"), (torch.float32, "f32")):
             es = 2 if dtype == torch.bfloat16 else 4
             for label, n in (("chunk", 8 << 20), ("1GiB", (1 << 30) // es)):
-                torch.manual_seed(5)
-                a = (torch.rand(n, device="cuda") + 0.5).to(dtype)
-                wire_in = pack((torch.rand(n, device="cuda") + 0.5).to(dtype))
-                out_p, out_f = torch.empty_like(a), torch.empty_like(a)
-                wire_p, wire_f = torch.empty_like(wire_in), torch.empty_like(wire_in)
+                for plain in ((False, True) if codec == "mxfp4" else (False,)):
+                    torch.manual_seed(5)
+                    a = (torch.rand(n, device="cuda") + 0.5).to(dtype)
+                    b = (torch.rand(n, device="cuda") + 0.5).to(dtype)
+                    second = b if plain else pack(b)
+                    w = _nbytes(codec, n)
+                    out_p, out_f = torch.empty_like(a), torch.empty_like(a)
+                    wire_p, wire_f = (torch.empty(w, device="cuda", dtype=torch.uint8)
+                                      for _ in range(2))
+                    combine, fused_op = (ops.axpby, axpby2_pack) if plain \
+                        else (axpby, axpby_pack)
 
-                def pair():
-                    axpby(a, wire_in, alpha, beta, dst=out_p)
-                    pack(out_p, out=wire_p)
+                    def pair():
+                        combine(a, second, alpha, beta, dst=out_p)
+                        pack(out_p, out=wire_p)
 
-                def fused():
-                    axpby_pack(a, wire_in, alpha, beta, dst=out_f, wire_out=wire_f)
+                    def fused():
+                        fused_op(a, second, alpha, beta, dst=out_f, wire_out=wire_f)
 
-                iters = args.iters * (8 if label == "chunk" else 1)
-                ts = _time_alternating({"pair": pair, "fused": fused}, iters,
-                                       args.warmup)
-                w = wire_in.numel()
-                nbytes = {"pair": 3 * n * es + 2 * w, "fused": 2 * n * es + 2 * w}
-                entry = {"elems": n}
-                for k, t in ts.items():
-                    med = statistics.median(t)
-                    entry[k] = {"median_us": round(med * 1e6, 1),
-                                "min_us": round(t[0] * 1e6, 1),
-                                "max_us": round(t[-1] * 1e6, 1),
-                                "gb_per_s": round(nbytes[k] / med / 1e9, 1)}
-                    print(f"{codec} {name} {label:5s} {k:5s} median {med*1e6:9.1f} us  "
-                          f"[{t[0]*1e6:.1f} .. {t[-1]*1e6:.1f}]  "
-                          f"{nbytes[k]/med/1e9:7.0f} GB/s (read+written)")
-                entry["pair_over_fused"] = round(
-                    statistics.median(ts["pair"]) / statistics.median(ts["fused"]), 3)
-                # the plan relies on identity, not closeness
-                bits = torch.int16 if es == 2 else torch.int32
-                assert torch.equal(out_p.view(bits), out_f.view(bits))
-                assert torch.equal(wire_p, wire_f)
-                result[f"{codec}_{name}_{label}"] = entry
-                del a, wire_in, out_p, out_f, wire_p, wire_f
+                    iters = args.iters * (8 if label == "chunk" else 1)
+                    ts = _time_alternating({"pair": pair, "fused": fused}, iters,
+                                           args.warmup)
+                    rd = n * es + (n * es if plain else w)  # the fused op's reads
+                    nbytes = {"pair": rd + 2 * n * es + w, "fused": rd + n * es + w}
+                    key = f"{codec}_{name}_{label}" + ("_plain" if plain else "")
+                    entry = {"elems": n}
+                    for k, t in ts.items():
+                        med = statistics.median(t)
+                        entry[k] = {"median_us": round(med * 1e6, 1),
+                                    "min_us": round(t[0] * 1e6, 1),
+                                    "max_us": round(t[-1] * 1e6, 1),
+                                    "gb_per_s": round(nbytes[k] / med / 1e9, 1)}
+                        print(f"{key:24s} {k:5s} median {med*1e6:9.1f} us  "
+                              f"[{t[0]*1e6:.1f} .. {t[-1]*1e6:.1f}]  "
+                              f"{nbytes[k]/med/1e9:7.0f} GB/s (read+written)", flush=True)
+                    entry["pair_over_fused"] = round(
+                        statistics.median(ts["pair"]) / statistics.median(ts["fused"]), 3)
+                    # the plan relies on identity, not closeness
+                    bits = torch.int16 if es == 2 else torch.int32
+                    assert torch.equal(out_p.view(bits), out_f.view(bits))
+                    assert torch.equal(wire_p, wire_f)
+                    result[key] = entry
+                    del a, b, second, out_p, out_f, wire_p, wire_f
     print(json.dumps(result))
 
 
@@ -204,6 +218,8 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["codec", "axpby", "forward"], default="codec")
     ap.add_argument("--codec", choices=sorted(_PREFIX), default="mxfp8")
+    ap.add_argument("--forward-codec", choices=sorted(_PREFIX) + ["all"], default="all",
+                    help="forward mode: the codec to time")
     ap.add_argument("--melems", type=int, default=64,
                     help="axpby mode: Mi elements per buffer")
     ap.add_argument("--mib", type=int, default=1024, help="tensor buffer size")

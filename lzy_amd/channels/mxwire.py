@@ -32,8 +32,8 @@ functions above for CPU ones.  ``wire_fused(name)`` maps a wire name to them.
 The ``mx4_*`` functions are the three layers for MXFP4: e2m1 nibbles, two
 per byte, ``uint8[17*nblk]`` (``mx4_nbytes``): half the link bytes of the
 8-bit wires at about four times the error of MXFP8.  ``wire_nbytes(name,
-numel)`` sizes a buffer of any wire; a forwarding node on this wire runs the
-combine and the pack as two steps.
+numel)`` sizes a buffer of any wire; a forwarding node on this wire is one
+kernel too (``lzy_amd.ops.mx4_axpby_pack`` / ``mx4_axpby2_pack``).
 """
 from __future__ import annotations
 
@@ -438,36 +438,20 @@ def mxi8_axpby2_pack(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
                        alpha, beta, dst, wire_out)
 
 
-def _then_pack(dst: torch.Tensor, wire_out: Optional[torch.Tensor]):
-    packed = mx4_pack(dst)
-    if wire_out is None:
-        return dst, packed
-    wire_out.copy_(packed)
-    return dst, wire_out
-
-
 def mx4_axpby_pack(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
                    beta: float = 1.0, dst: Optional[torch.Tensor] = None,
                    wire_out: Optional[torch.Tensor] = None):
-    """:func:`mx8_axpby_pack` for MXFP4 buffers, as its two steps:
-    :func:`mx4_axpby`, then :func:`mx4_pack` of ``dst`` (no fused kernel)."""
-    return _then_pack(mx4_axpby(a, wire, alpha, beta, dst), wire_out)
+    """:func:`mx8_axpby_pack` for MXFP4 buffers."""
+    return _axpby_pack("mx4_axpby_pack", mx4_axpby_torch, mx4_pack_torch, a, wire,
+                       alpha, beta, dst, wire_out)
 
 
 def mx4_axpby2_pack(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
                     beta: float = 1.0, dst: Optional[torch.Tensor] = None,
                     wire_out: Optional[torch.Tensor] = None):
-    """:func:`mx8_axpby2_pack` with an MXFP4 ``wire_out``, as its two steps:
-    the plain combine (``ops.axpby`` for device tensors), then the pack."""
-    if _native(a):
-        from lzy_amd import ops
-
-        return _then_pack(ops.axpby(a, b, alpha, beta, dst=dst), wire_out)
-    r = _axpby2_torch(a, b, alpha, beta, a.dtype if dst is None else dst.dtype)
-    if dst is None:
-        return _then_pack(r, wire_out)
-    dst.copy_(r)
-    return _then_pack(dst, wire_out)
+    """:func:`mx8_axpby2_pack` with an MXFP4 ``wire_out``."""
+    return _axpby_pack("mx4_axpby2_pack", _axpby2_torch, mx4_pack_torch, a, b,
+                       alpha, beta, dst, wire_out)
 
 
 # wire name (channel_wire_cast, stream_wire_cast, a plan's "wire") -> the

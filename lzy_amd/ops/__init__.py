@@ -28,6 +28,8 @@ _MXI8 = False  # ... and lz_mxi8_pack / lz_mxi8_unpack / lz_mxi8_axpby (MXINT8)
 # fused combine + re-encode of a forwarding merge-tree node)
 _MX_AXPBY_PACK = False
 _MX4 = False  # ... and lz_mx4_pack / lz_mx4_unpack / lz_mx4_axpby (MXFP4)
+# ... and lz_mx4_axpby_pack / lz_mx4_axpby2_pack (the forwarding node on MXFP4)
+_MX4_AXPBY_PACK = False
 _SEGCOPY = False  # ... and lz_segcopy (the packed-bundle gather/scatter)
 # bytes per tile of the segmented copy — LZ_SEG_TILE in hipops.hip
 SEGCOPY_TILE = 16384
@@ -200,6 +202,23 @@ def _try_load() -> Optional[ctypes.CDLL]:
         _MX4 = True
     except AttributeError:
         _MX4 = False
+    global _MX4_AXPBY_PACK
+    try:
+        lib.lz_mx4_axpby_pack.restype = ctypes.c_int
+        lib.lz_mx4_axpby_pack.argtypes = [
+            ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
+            ctypes.c_float, ctypes.c_void_p,
+        ]
+        lib.lz_mx4_axpby2_pack.restype = ctypes.c_int
+        lib.lz_mx4_axpby2_pack.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+            ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float,
+            ctypes.c_float, ctypes.c_void_p,
+        ]
+        _MX4_AXPBY_PACK = True
+    except AttributeError:
+        _MX4_AXPBY_PACK = False
     global _SEGCOPY
     try:
         lib.lz_segcopy.restype = ctypes.c_int
@@ -346,7 +365,7 @@ def _mx_entry(op: str):
         return getattr(_require_mx8(), "lz_" + op)
     lib = _require_native()
     if op.endswith("_pack") and "axpby" in op:
-        present = _MX_AXPBY_PACK
+        present = _MX4_AXPBY_PACK if op.startswith("mx4_") else _MX_AXPBY_PACK
     elif op.startswith("mx4_"):
         present = _MX4
     else:
@@ -585,6 +604,23 @@ def mxi8_axpby2_pack(a, b, alpha: float = 1.0, beta: float = 1.0, dst=None,
     return _mx_axpby_pack("mxi8_axpby2_pack", a, b, alpha, beta, dst, wire_out)
 
 
+def mx4_axpby_pack(a, wire, alpha: float = 1.0, beta: float = 1.0, dst=None,
+                   wire_out=None):
+    """:func:`mx4_axpby` and :func:`mx4_pack` of its result in one launch:
+    :func:`mx8_axpby_pack` for MXFP4.  ``wire`` and ``wire_out`` are
+    ``uint8[mx4_nbytes(a.numel())]``.  ``dst`` is ``mx4_axpby``'s bit for
+    bit (an f16 ``dst`` is the fp32 result rounded again, on every path),
+    ``wire_out`` byte for byte ``mx4_pack(dst)``."""
+    return _mx_axpby_pack("mx4_axpby_pack", a, wire, alpha, beta, dst, wire_out)
+
+
+def mx4_axpby2_pack(a, b, alpha: float = 1.0, beta: float = 1.0, dst=None,
+                    wire_out=None):
+    """:func:`mx8_axpby2_pack` with an MXFP4 ``wire_out``: ``dst`` is
+    :func:`axpby`'s bit for bit, ``wire_out`` is ``mx4_pack(dst)``."""
+    return _mx_axpby_pack("mx4_axpby2_pack", a, b, alpha, beta, dst, wire_out)
+
+
 def _mx_axpby_pack(op: str, a, second, alpha, beta, dst, wire_out):
     import torch
 
@@ -593,7 +629,7 @@ def _mx_axpby_pack(op: str, a, second, alpha, beta, dst, wire_out):
         raise ValueError(f"{op} requires device tensors")
     _mx8_check_dtype(a.dtype, op)
     n = a.numel()
-    nbytes = mx8_nbytes(n)
+    nbytes = _mx_nbytes(op, n)
     if plain:
         if second.numel() != n or second.dtype != a.dtype:
             raise ValueError(f"{op}: shape/dtype mismatch")

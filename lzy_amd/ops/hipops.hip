@@ -1797,6 +1797,251 @@ extern "C" hipError_t lz_mx4_axpby(const void* a, int a_dtype, const void* wire_
 }
 
 // ---------------------------------------------------------------------------
+// mx4_axpby_pack / mx4_axpby2_pack: the step of a merge-tree node that
+// forwards on the MXFP4 wire (docs/mxwire.md, "Forwarding nodes"), in one pass:
+//   dst      = cast(alpha*a + beta*x)   x = decode(wire_in), or a plain b
+//   wire_out = mx4_pack(dst)
+// lz_mx4_axpby followed by lz_mx4_pack of its result moves 7.06 B/element of
+// bf16 through HBM in two launches; here the value is encoded while it is
+// still in registers: 5.06 B/element (2 + 17/32 read, 2 + 17/32 written).
+//
+// dst is lz_mx4_axpby's (axpby_kernel's) value bit for bit and wire_out byte
+// for byte what lz_mx4_pack makes of that dst: lz_mx4_emit is handed the value
+// already rounded to DstT and widened back to fp32, +0.0 at positions >= n
+// whatever the padding nibbles and the scale byte of wire_in decode to.
+//
+// Work split as in the rest of this section: a lane owns 8 elements (one
+// payload dword in, one out), a quad a block, a wave 16 blocks.  The encode
+// half crosses lanes, so the loop is mx4_pack_kernel's: g0 and every branch
+// on it are wave-uniform, two groups per trip, and a lane whose group lies
+// past the tensor goes through the encoder with zeros.  On the unguarded
+// path the two payload dwords, the two scale bytes and the 16 B loads of a
+// (and b) of both groups issue before any is consumed.  The four lanes of a
+// quad each load their block's input scale byte (a wave reads 16 contiguous
+// bytes, issued among the other loads); docs/performance.md has the rates.
+//
+// dst may be a (a lane reads its 8 elements before it writes them);
+// wire_out must not overlap any other argument.
+// ---------------------------------------------------------------------------
+
+// the second operand of one group, loaded and not yet consumed: the payload
+// dword and scale byte of a wire (WIRE), or 8 plain elements as fp32
+struct LzMx4Second {
+    uint32_t w, b;
+    float f[8];
+};
+
+template <typename SrcT, bool WIRE, bool ALIGNED, bool FULL>
+__device__ __forceinline__ void lz_mx4f_fetch(const void* src2,
+                                              const uint8_t* __restrict__ scales_in,
+                                              int64_t g, int64_t n, LzMx4Second& s) {
+    if constexpr (WIRE) {
+        // the payload dword of the padded tail exists: [0, 16*nblk)
+        s.w = lz_mx4_payload<ALIGNED>(static_cast<const uint8_t*>(src2), g);
+        s.b = scales_in[g >> 2];
+    } else {
+        lz_mx8_load<SrcT, FULL>(static_cast<const SrcT*>(src2), g * 8, n, s.f);
+    }
+}
+
+// combine one group, store it to dst and leave in r what the encoder sees:
+// the stored value as fp32, +0.0 at positions >= n.  FULL: all 8 elements
+// lie inside [0, n) and dst + e0 is 16 B-aligned.
+//
+// TWO_STEP (f16 dst only): the fp32 FMA result is a value of its own (the
+// empty asm), so the f16 convert rounds a second time and cannot fuse with
+// the FMA into one single-rounding v_fma_mixlo_f16.  mx4_decode_kernel does
+// so on every path; axpby_kernel on every whole group, while the elements of
+// a group cut by n take its fused tail loop.
+template <typename DstT, bool WIRE, bool FULL, bool TWO_STEP>
+__device__ __forceinline__ void lz_mx4f_combine(const float (&fa)[8],
+                                                const LzMx4Second& s, DstT* dst,
+                                                int64_t e0, int64_t n, float alpha,
+                                                float beta, float (&r)[8]) {
+    constexpr int V = 8;
+    float x[V];
+    if constexpr (WIRE) {
+        // the block scale is the converts' E8M0 operand: 0xff decodes every
+        // nibble to NaN, 0 to steps of 2^-127, with no multiply
+        const float scale = __uint_as_float(s.b << 23);
+        const lz_f32x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(s.w, scale, 0);
+        const lz_f32x2 p1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(s.w, scale, 1);
+        const lz_f32x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(s.w, scale, 2);
+        const lz_f32x2 p3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(s.w, scale, 3);
+        x[0] = p0.x, x[1] = p0.y, x[2] = p1.x, x[3] = p1.y;
+        x[4] = p2.x, x[5] = p2.y, x[6] = p3.x, x[7] = p3.y;
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) x[k] = s.f[k];
+    }
+    DstT y[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        float t = fmaf(fa[k], alpha, x[k] * beta);
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (TWO_STEP && std::is_same<DstT, __half>::value)
+            asm volatile("" : "+v"(t));
+#endif
+        y[k] = lz_from_float<DstT>(t);
+        r[k] = (FULL || e0 + k < n) ? lz_to_float<DstT>(y[k]) : 0.f;
+    }
+    if (FULL) {
+        LzVec16 q[sizeof(DstT) * V / 16];
+        __builtin_memcpy(q, y, sizeof(y));
+        LzVec16* p = reinterpret_cast<LzVec16*>(dst + e0);
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(DstT) * V / 16); ++k) p[k] = q[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            if (e0 + k < n) dst[e0 + k] = y[k];
+    }
+}
+
+// one group on the guarded path (the tail, and element-aligned views).  The
+// branch is per lane and closes before the caller's cross-lane encode: a
+// lane whose group lies past n loads and stores nothing and hands on +0.0.
+template <typename SrcT, typename DstT, bool WIRE, bool ALIGNED>
+__device__ __forceinline__ void lz_mx4f_one(const SrcT* a, const void* src2,
+                                            const uint8_t* __restrict__ scales_in,
+                                            DstT* dst, int64_t g, int64_t n, float alpha,
+                                            float beta, float (&r)[8]) {
+    const int64_t e0 = g * 8;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = 0.f;
+    if (e0 >= n) return;
+    LzMx4Second s;
+    float fa[8];
+    if (ALIGNED && e0 + 8 <= n) {
+        lz_mx4f_fetch<SrcT, WIRE, ALIGNED, true>(src2, scales_in, g, n, s);
+        lz_mx8_load<SrcT, true>(a, e0, n, fa);
+        lz_mx4f_combine<DstT, WIRE, true, true>(fa, s, dst, e0, n, alpha, beta, r);
+    } else {
+        lz_mx4f_fetch<SrcT, WIRE, ALIGNED, false>(src2, scales_in, g, n, s);
+        lz_mx8_load<SrcT, false>(a, e0, n, fa);
+        if (WIRE || e0 + 8 <= n)
+            lz_mx4f_combine<DstT, WIRE, false, true>(fa, s, dst, e0, n, alpha, beta, r);
+        else
+            lz_mx4f_combine<DstT, WIRE, false, false>(fa, s, dst, e0, n, alpha, beta, r);
+    }
+}
+
+template <typename SrcT, typename DstT, bool WIRE, bool ALIGNED>
+__global__ void __launch_bounds__(LZ_BLOCK) LZ_NO_PK_F32
+mx4_axpby_pack_kernel(const SrcT* a, const void* src2, DstT* dst,
+                      uint8_t* __restrict__ wire_out, int64_t n, float alpha,
+                      float beta) {
+    const int64_t nblk = (n + 31) >> 5;
+    const int64_t ngroups = nblk * 4;
+    const uint8_t* __restrict__ scales_in =
+        WIRE ? static_cast<const uint8_t*>(src2) + nblk * 16 : nullptr;
+    uint8_t* __restrict__ scales_out = wire_out + nblk * 16;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+
+    for (int64_t g0 = (int64_t)blockIdx.x * blockDim.x + wave * 64; g0 < ngroups;
+         g0 += 2 * stride) {
+        const int64_t ga = g0 + lane, gb = ga + stride;
+        float ra[8], rb[8];
+        if (ALIGNED && (g0 + stride + 64) * 8 <= n) {  // both groups of all 64 lanes whole
+            LzMx4Second sa, sb;
+            float fa[8], fb[8];
+            lz_mx4f_fetch<SrcT, WIRE, true, true>(src2, scales_in, ga, n, sa);
+            lz_mx4f_fetch<SrcT, WIRE, true, true>(src2, scales_in, gb, n, sb);
+            lz_mx8_load<SrcT, true>(a, ga * 8, n, fa);
+            lz_mx8_load<SrcT, true>(a, gb * 8, n, fb);
+            // left alone the scheduler sinks the second group's load of a
+            // behind the first group's wait, to reuse its registers
+            __builtin_amdgcn_sched_barrier(0);
+            lz_mx4f_combine<DstT, WIRE, true, true>(fa, sa, dst, ga * 8, n, alpha, beta,
+                                                    ra);
+            lz_mx4f_combine<DstT, WIRE, true, true>(fb, sb, dst, gb * 8, n, alpha, beta,
+                                                    rb);
+            lz_mx4_emit<true, true>(ra, ga, lane, ngroups, nblk, wire_out, scales_out);
+            lz_mx4_emit<true, true>(rb, gb, lane, ngroups, nblk, wire_out, scales_out);
+        } else {
+            const bool two = g0 + stride < ngroups;  // wave-uniform
+            lz_mx4f_one<SrcT, DstT, WIRE, ALIGNED>(a, src2, scales_in, dst, ga, n, alpha,
+                                                   beta, ra);
+            lz_mx4_emit<ALIGNED, false>(ra, ga, lane, ngroups, nblk, wire_out,
+                                        scales_out);
+            if (two) {
+                lz_mx4f_one<SrcT, DstT, WIRE, ALIGNED>(a, src2, scales_in, dst, gb, n,
+                                                       alpha, beta, rb);
+                lz_mx4_emit<ALIGNED, false>(rb, gb, lane, ngroups, nblk, wire_out,
+                                            scales_out);
+            }
+        }
+    }
+}
+
+// a, dst: n elements of a_dtype / dst_dtype (both f32/f16/bf16); src2: the
+// MXFP4 wire of n elements (WIRE) or n more elements of a_dtype; wire_out:
+// 17*ceil(n/32) bytes.  dst == a is allowed; wire_out overlaps nothing.
+template <bool WIRE>
+static hipError_t lz_mx4_axpby_pack_launch(const void* a, int a_dtype, const void* src2,
+                                           void* dst, int dst_dtype, void* wire_out,
+                                           int64_t n, float alpha, float beta,
+                                           void* stream) {
+    if (!lz_mx_float_dtype(a_dtype) || !lz_mx_float_dtype(dst_dtype) || n < 0)
+        return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    const int blocks = lz_mx8_grid(n);
+    const bool aligned = (((uintptr_t)a & 15) == 0) && (((uintptr_t)dst & 15) == 0) &&
+                         (((uintptr_t)src2 & (WIRE ? 3 : 15)) == 0) &&
+                         (((uintptr_t)wire_out & 3) == 0);
+#define LZ_MX4F_LAUNCH(AL)                                                      \
+    hipLaunchKernelGGL((mx4_axpby_pack_kernel<S, D, WIRE, AL>), dim3(blocks),   \
+                       dim3(LZ_BLOCK), 0, s, (const S*)a, src2, (D*)dst,        \
+                       (uint8_t*)wire_out, n, alpha, beta)
+#define LZ_MX4F_DST(SrcT, code, DstT)                                           \
+    case code: {                                                                \
+        using S = SrcT;                                                         \
+        using D = DstT;                                                         \
+        if (aligned) LZ_MX4F_LAUNCH(true);                                      \
+        else LZ_MX4F_LAUNCH(false);                                             \
+        break;                                                                  \
+    }
+#define LZ_MX4F_SRC(scode, SrcT)                                                \
+    case scode:                                                                 \
+        switch (dst_dtype) {                                                    \
+            LZ_MX4F_DST(SrcT, LZ_F32, float)                                    \
+            LZ_MX4F_DST(SrcT, LZ_F16, __half)                                   \
+            LZ_MX4F_DST(SrcT, LZ_BF16, __hip_bfloat16)                          \
+            default: return hipErrorInvalidValue;                               \
+        }                                                                       \
+        break;
+    switch (a_dtype) {
+        LZ_MX4F_SRC(LZ_F32, float)
+        LZ_MX4F_SRC(LZ_F16, __half)
+        LZ_MX4F_SRC(LZ_BF16, __hip_bfloat16)
+        default: return hipErrorInvalidValue;
+    }
+#undef LZ_MX4F_SRC
+#undef LZ_MX4F_DST
+#undef LZ_MX4F_LAUNCH
+    return hipGetLastError();
+}
+
+extern "C" hipError_t lz_mx4_axpby_pack(const void* a, int a_dtype, const void* wire_in,
+                                        void* dst, int dst_dtype, void* wire_out,
+                                        int64_t n, float alpha, float beta,
+                                        void* stream) {
+    return lz_mx4_axpby_pack_launch<true>(a, a_dtype, wire_in, dst, dst_dtype, wire_out,
+                                          n, alpha, beta, stream);
+}
+
+extern "C" hipError_t lz_mx4_axpby2_pack(const void* a, const void* b, int src_dtype,
+                                         void* dst, int dst_dtype, void* wire_out,
+                                         int64_t n, float alpha, float beta,
+                                         void* stream) {
+    return lz_mx4_axpby_pack_launch<false>(a, src_dtype, b, dst, dst_dtype, wire_out, n,
+                                           alpha, beta, stream);
+}
+
+// ---------------------------------------------------------------------------
 // mx8_axpby_pack / mx8_axpby2_pack: the step of a merge-tree node that
 // forwards (docs/mxwire.md, "Forwarding nodes"), in one pass:
 //   dst      = cast(alpha*a + beta*x)   x = decode(wire_in), or a plain b
