@@ -4,6 +4,9 @@ ones named below; ``--compare-lib`` always adds the other build's
 ``lz_mx8_*``, which move the same bytes.  ``--codec mxfp4`` times
 ``mx4_pack``, ``mx4_unpack`` and ``mx4_axpby`` (17/32 B per element on the
 wire side) and, in the same rounds, this build's ``mx8_*`` three.
+``--codec mxfp6`` does the same for ``mx6_pack``, ``mx6_unpack`` and
+``mx6_axpby`` (25/32 B per element on the wire side), with the ``mx8_*`` and
+the ``mx4_*`` three in its rounds.
 
 On a 1 GiB bf16 buffer (``--dtype f16`` / ``f32``: as many bytes of that
 type), times in one process, interleaved round-robin:
@@ -150,7 +153,7 @@ def forward_mode(args) -> None:
     at the default stream_chunk_mb) and on a 1 GiB operand."""
     alpha, beta = 0.5, 0.5
     result = {"mode": "forward", "iters": args.iters}
-    codecs = _PREFIX if args.forward_codec == "all" else (args.forward_codec,)
+    codecs = _FORWARD if args.forward_codec == "all" else (args.forward_codec,)
     for codec in codecs:
         pre = _PREFIX[codec]
         pack, axpby, axpby_pack, axpby2_pack = (
@@ -207,10 +210,14 @@ def forward_mode(args) -> None:
 
 
 _DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
-_PREFIX = {"mxfp8": "mx8", "mxint8": "mxi8", "mxfp4": "mx4"}
+_PREFIX = {"mxfp8": "mx8", "mxint8": "mxi8", "mxfp4": "mx4", "mxfp6": "mx6"}
+# the codecs with a fused forwarding kernel (mxfp6 runs the two steps)
+_FORWARD = ("mxfp8", "mxint8", "mxfp4")
 
 
 def _nbytes(codec: str, n: int) -> int:
+    if codec == "mxfp6":
+        return ops.mx6_nbytes(n)
     return ops.mx4_nbytes(n) if codec == "mxfp4" else ops.mx8_nbytes(n)
 
 
@@ -218,7 +225,7 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["codec", "axpby", "forward"], default="codec")
     ap.add_argument("--codec", choices=sorted(_PREFIX), default="mxfp8")
-    ap.add_argument("--forward-codec", choices=sorted(_PREFIX) + ["all"], default="all",
+    ap.add_argument("--forward-codec", choices=sorted(_FORWARD) + ["all"], default="all",
                     help="forward mode: the codec to time")
     ap.add_argument("--melems", type=int, default=64,
                     help="axpby mode: Mi elements per buffer")
@@ -261,19 +268,28 @@ def main() -> None:
         f"cast_{dname}_to_e4m3": (lambda: ops.cast_copy(src, fp8), es * n + n),
         f"cast_e4m3_to_{dname}": (lambda: ops.cast_copy(fp8, back), n + es * n),
     }
-    if args.codec == "mxfp4":
-        # the 8-bit kernels and both decode-combines, in the same rounds
-        wire8 = ops.mx8_pack(src)
+    if args.codec in ("mxfp4", "mxfp6"):
+        # the 8-bit kernels (mxfp6: the 4-bit ones too) and every
+        # decode-combine, in the same rounds
         acc = torch.empty_like(src)
-        cases.update({
-            "mx8_pack": (lambda: ops.mx8_pack(src, out=wire8), es * n + wire8.numel()),
-            "mx8_unpack": (lambda: ops.mx8_unpack(wire8, n, dtype, out=back),
-                           wire8.numel() + es * n),
-            "mx4_axpby": (lambda: ops.mx4_axpby(src, wire, 0.5, 0.5, dst=acc),
-                          2 * es * n + wire.numel()),
-            "mx8_axpby": (lambda: ops.mx8_axpby(src, wire8, 0.5, 0.5, dst=acc),
-                          2 * es * n + wire8.numel()),
-        })
+        axpby = getattr(ops, f"{pre}_axpby")
+        cases[f"{pre}_axpby"] = (lambda: axpby(src, wire, 0.5, 0.5, dst=acc),
+                                 2 * es * n + wire.numel())
+
+        def add_codec(o, wire_o):
+            o_pack, o_unpack, o_axpby = (getattr(ops, f"{o}_{k}")
+                                         for k in ("pack", "unpack", "axpby"))
+            cases.update({
+                f"{o}_pack": (lambda: o_pack(src, out=wire_o), es * n + wire_o.numel()),
+                f"{o}_unpack": (lambda: o_unpack(wire_o, n, dtype, out=back),
+                                wire_o.numel() + es * n),
+                f"{o}_axpby": (lambda: o_axpby(src, wire_o, 0.5, 0.5, dst=acc),
+                               2 * es * n + wire_o.numel()),
+            })
+
+        add_codec("mx8", ops.mx8_pack(src))
+        if args.codec == "mxfp6":
+            add_codec("mx4", ops.mx4_pack(src))
     if args.compare_lib:
         other = ctypes.CDLL(args.compare_lib)
         other.lz_mx8_unpack.restype = ctypes.c_int

@@ -1,4 +1,4 @@
-"""Block-scaled wire codecs (OCP MXFP8, MXINT8 and MXFP4; format spec:
+"""Block-scaled wire codecs (OCP MXFP8, MXINT8, MXFP4 and MXFP6; format spec:
 docs/mxwire.md).
 
 Every 32 consecutive elements share one power-of-two scale byte (E8M0)
@@ -34,6 +34,11 @@ per byte, ``uint8[17*nblk]`` (``mx4_nbytes``): half the link bytes of the
 8-bit wires at about four times the error of MXFP8.  ``wire_nbytes(name,
 numel)`` sizes a buffer of any wire; a forwarding node on this wire is one
 kernel too (``lzy_amd.ops.mx4_axpby_pack`` / ``mx4_axpby2_pack``).
+
+The ``mx6_*`` functions are the three layers for MXFP6: 6-bit e2m3 codes,
+four in three bytes, ``uint8[25*nblk]`` (``mx6_nbytes``): the error of MXFP8
+at 24 % fewer link bytes.  A forwarding node on this wire is the combine
+kernel followed by the pack kernel (``mx6_axpby_pack`` / ``mx6_axpby2_pack``).
 """
 from __future__ import annotations
 
@@ -51,6 +56,10 @@ def mx8_nbytes(numel: int) -> int:
 
 def mx4_nbytes(numel: int) -> int:
     return 17 * ((int(numel) + MX_BLOCK - 1) // MX_BLOCK)
+
+
+def mx6_nbytes(numel: int) -> int:
+    return 25 * ((int(numel) + MX_BLOCK - 1) // MX_BLOCK)
 
 
 def _numel(shape: Sequence[int]) -> int:
@@ -229,6 +238,69 @@ def mx4_unpack_torch(buf: torch.Tensor, shape: Union[int, Sequence[int]],
     return bits.view(torch.float32).reshape(-1)[:n].to(dtype).reshape(shape)
 
 
+def mx6_pack_torch(t: torch.Tensor) -> torch.Tensor:
+    """Encode ``t`` (f32/bf16/f16, any device) as MXFP6 (e2m3) with torch
+    ops only."""
+    x, amax, out = _blocks(t, "mx6_pack", 25)
+    nblk = x.shape[0]
+    if nblk == 0:
+        return out
+    nan = ((x.view(torch.int32) & 0x7FFFFFFF) > 0x7F800000).any(dim=1)
+    # smallest 2^(b-127) with amax / 2^(b-127) <= 7.5 = 1.875 * 2^2: E - 2, one
+    # more from m = 0x700001 on (the add carries into the exponent then)
+    b = (((amax + 0x0FFFFF) >> 23) - 2).clamp_(min=0)
+    v = x * ((254 - b) << 23).view(torch.float32)[:, None]  # exact, or -> 0
+    # e2m3 code of |v| on its bits, clamped to 7.5 (moves +-Inf only).  From
+    # 1.0 on the code is the exponent (rebiased 127 -> 1) and the top three
+    # mantissa bits, rounded to nearest even on the 20 bits below (a carry
+    # walks into the exponent).  Below 1.0 the grid is k/8: adding 1.5 * 2^23
+    # to 8|v| (exact) rounds to an integer by the add's own RNE and leaves it
+    # in the low bits of the sum; 8 there is the code of 1.0 all the same.
+    a = (v.view(torch.int32) & 0x7FFFFFFF).clamp(max=0x40F00000)
+    hi = ((a + 0x7FFFF + ((a >> 20) & 1)) >> 20) - 1008
+    lo = (a.view(torch.float32) * 8.0 + 12582912.0).view(torch.int32) & 0xFF
+    q = torch.where(a >= 0x3F800000, hi, lo) | ((x.view(torch.int32) >> 26) & 0x20)
+    q = torch.where(nan[:, None], torch.zeros_like(q), q).view(nblk, 8, 4)
+    # four codes are three bytes, little-endian
+    w = q[..., 0] | (q[..., 1] << 6) | (q[..., 2] << 12) | (q[..., 3] << 18)
+    out[: 24 * nblk] = torch.stack(
+        [w & 0xFF, (w >> 8) & 0xFF, w >> 16], dim=2).to(torch.uint8).reshape(-1)
+    out[24 * nblk:] = torch.where(nan, torch.full_like(b, 0xFF), b).to(torch.uint8)
+    return out
+
+
+def mx6_unpack_torch(buf: torch.Tensor, shape: Union[int, Sequence[int]],
+                     dtype: torch.dtype) -> torch.Tensor:
+    """Decode an MXFP6 wire buffer into a tensor of ``shape``/``dtype``."""
+    if dtype not in _MX_DTYPES:
+        raise ValueError(f"mx6_unpack: dtype must be f32/bf16/f16, got {dtype}")
+    shape = (int(shape),) if isinstance(shape, int) else tuple(shape)
+    n = _numel(shape)
+    nblk = (n + MX_BLOCK - 1) // MX_BLOCK
+    if buf.dtype != torch.uint8 or buf.numel() != 25 * nblk:
+        raise ValueError(
+            f"mx6_unpack: buffer must be uint8[{25 * nblk}] for {n} elements, "
+            f"got {buf.dtype}[{buf.numel()}]"
+        )
+    if n == 0:
+        return torch.empty(shape, dtype=dtype, device=buf.device)
+    buf = buf.reshape(-1)
+    p = buf[: 24 * nblk].to(torch.int32).view(nblk, 8, 3)
+    w = p[..., 0] | (p[..., 1] << 8) | (p[..., 2] << 16)
+    q = torch.stack([(w >> s) & 0x3F for s in (0, 6, 12, 18)], dim=2).view(nblk, MX_BLOCK)
+    b = buf[24 * nblk:].to(torch.int32)[:, None]
+    # |e2m3| as fp32 bits: codes from 8 on are exponent c>>3 (bias 1) and
+    # mantissa c&7; codes below are the subnormals c/8
+    c = q & 0x1F
+    mag = torch.where(c >= 8, (((c >> 3) + 126) << 23) | ((c & 7) << 20),
+                      (c.to(torch.float32) * 0.125).view(torch.int32))
+    mult = torch.where(b > 0, b << 23, torch.full_like(b, 0x00400000))
+    x = mag.to(torch.int32).view(torch.float32) * mult.to(torch.int32).view(torch.float32)
+    bits = x.view(torch.int32) | ((q & 0x20) << 26)  # the sign, of a zero too
+    bits = torch.where(b == 0xFF, torch.full_like(bits, 0x7FC00000), bits)
+    return bits.view(torch.float32).reshape(-1)[:n].to(dtype).reshape(shape)
+
+
 def _f32(v: float) -> float:
     # the kernel takes alpha/beta as C floats
     return float(torch.tensor(float(v), dtype=torch.float32))
@@ -263,6 +335,14 @@ def mx4_axpby_torch(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
                     out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """:func:`mx8_axpby_torch` for an MXFP4 ``wire``."""
     return _axpby_torch("mx4_axpby", mx4_unpack_torch, a, wire, alpha, beta,
+                        out_dtype)
+
+
+def mx6_axpby_torch(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
+                    beta: float = 1.0,
+                    out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """:func:`mx8_axpby_torch` for an MXFP6 ``wire``."""
+    return _axpby_torch("mx6_axpby", mx6_unpack_torch, a, wire, alpha, beta,
                         out_dtype)
 
 
@@ -373,6 +453,22 @@ def mx4_axpby(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
     return _axpby("mx4_axpby", mx4_axpby_torch, a, wire, alpha, beta, dst)
 
 
+def mx6_pack(t: torch.Tensor) -> torch.Tensor:
+    return _pack("mx6_pack", mx6_pack_torch, t)
+
+
+def mx6_unpack(buf: torch.Tensor, shape: Union[int, Sequence[int]],
+               dtype: torch.dtype) -> torch.Tensor:
+    return _unpack("mx6_unpack", mx6_unpack_torch, buf, shape, dtype)
+
+
+def mx6_axpby(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
+              beta: float = 1.0,
+              dst: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`mx8_axpby` for an MXFP6 ``wire``."""
+    return _axpby("mx6_axpby", mx6_axpby_torch, a, wire, alpha, beta, dst)
+
+
 def _axpby_pack(op: str, combine_torch: Callable, pack_torch: Callable, a, second,
                 alpha, beta, dst, wire_out):
     """The step of a forwarding merge-tree node: ``(dst, pack(dst))``.  One
@@ -454,20 +550,65 @@ def mx4_axpby2_pack(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
                        alpha, beta, dst, wire_out)
 
 
+def _mx6_then_pack(dst: torch.Tensor, wire_out: Optional[torch.Tensor]):
+    if _native(dst):
+        from lzy_amd import ops
+
+        return dst, ops.mx6_pack(dst, out=wire_out)
+    packed = mx6_pack_torch(dst)
+    if wire_out is None:
+        return dst, packed
+    wire_out.copy_(packed)
+    return dst, wire_out
+
+
+def mx6_axpby_pack(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
+                   beta: float = 1.0, dst: Optional[torch.Tensor] = None,
+                   wire_out: Optional[torch.Tensor] = None):
+    """:func:`mx8_axpby_pack` for MXFP6 buffers, as its two steps on every
+    device: :func:`mx6_axpby`, then :func:`mx6_pack` of ``dst`` (there is no
+    fused kernel on this wire yet)."""
+    return _mx6_then_pack(mx6_axpby(a, wire, alpha, beta, dst), wire_out)
+
+
+def mx6_axpby2_pack(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
+                    beta: float = 1.0, dst: Optional[torch.Tensor] = None,
+                    wire_out: Optional[torch.Tensor] = None):
+    """:func:`mx8_axpby2_pack` with an MXFP6 ``wire_out``, as its two steps:
+    the plain combine (``ops.axpby`` for device tensors), then the pack."""
+    if _native(a):
+        from lzy_amd import ops
+
+        return _mx6_then_pack(ops.axpby(a, b, alpha, beta, dst=dst), wire_out)
+    r = _axpby2_torch(a, b, alpha, beta, a.dtype if dst is None else dst.dtype)
+    if dst is None:
+        return _mx6_then_pack(r, wire_out)
+    if dst.shape != a.shape:
+        raise ValueError(
+            f"mx6_axpby2_pack: dst has shape {tuple(dst.shape)}, "
+            f"expected {tuple(a.shape)}"
+        )
+    dst.copy_(r)
+    return _mx6_then_pack(dst, wire_out)
+
+
 # wire name (channel_wire_cast, stream_wire_cast, a plan's "wire") -> the
 # dispatching (pack, unpack, axpby), and the size of its buffer
 _WIRE_CODECS = {
     "mxfp8": (mx8_pack, mx8_unpack, mx8_axpby),
     "mxint8": (mxi8_pack, mxi8_unpack, mxi8_axpby),
     "mxfp4": (mx4_pack, mx4_unpack, mx4_axpby),
+    "mxfp6": (mx6_pack, mx6_unpack, mx6_axpby),
 }
-_WIRE_NBYTES = {"mxfp8": mx8_nbytes, "mxint8": mx8_nbytes, "mxfp4": mx4_nbytes}
+_WIRE_NBYTES = {"mxfp8": mx8_nbytes, "mxint8": mx8_nbytes, "mxfp4": mx4_nbytes,
+                "mxfp6": mx6_nbytes}
 MX_WIRES = tuple(_WIRE_CODECS)
 # ... -> the dispatching (axpby_pack, axpby2_pack) of a forwarding node
 _WIRE_FUSED = {
     "mxfp8": (mx8_axpby_pack, mx8_axpby2_pack),
     "mxint8": (mxi8_axpby_pack, mxi8_axpby2_pack),
     "mxfp4": (mx4_axpby_pack, mx4_axpby2_pack),
+    "mxfp6": (mx6_axpby_pack, mx6_axpby2_pack),
 }
 
 

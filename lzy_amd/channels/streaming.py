@@ -37,11 +37,11 @@ def streamed_reduce_pair(
     its ``t`` in chunks and returns None.  Both sides must pass the same
     shape/dtype/chunk_bytes and the same ``wire``.
 
-    ``wire="mxfp8"``, ``"mxint8"`` or ``"mxfp4"`` (f32/bf16/f16 only): chunks are a
+    ``wire="mxfp8"``, ``"mxint8"``, ``"mxfp4"`` or ``"mxfp6"`` (f32/bf16/f16 only): chunks are a
     multiple of 256 elements and cross the link as self-contained buffers
     of that codec (docs/mxwire.md); the sender packs each one, the receiver
     combines with the codec's fused decode (``mx8_axpby``, ``mxi8_axpby``,
-    ``mx4_axpby``).
+    ``mx4_axpby``, ``mx6_axpby``).
     Device tensors on a gloo group are staged through the host as packed
     bytes: packed by the kernel before, combined by the kernel after.
     """

@@ -212,14 +212,14 @@ def _should_wirecast(dtype: torch.dtype, numel: int, wire) -> bool:
     )
 
 
-# "mxfp8", "mxint8" and "mxfp4" are not torch dtypes: the block-scaled codecs
+# "mxfp8", "mxint8", "mxfp4" and "mxfp6" are not torch dtypes: the block-scaled codecs
 # (channels/mxwire.py) pack into a flat uint8 buffer, which every path
 # carries — RCCL device, the host-staged fallback and CPU tensors over gloo.
 
 
 def wire_cast_mx() -> str:
     """The block-scaled codec ``channel_wire_cast`` names ("mxfp8",
-    "mxint8", "mxfp4"), or "" when it names none."""
+    "mxint8", "mxfp4", "mxfp6"), or "" when it names none."""
     from lzy_amd.channels.mxwire import MX_WIRES
     from lzy_amd.config import get_config
 

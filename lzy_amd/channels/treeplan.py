@@ -29,12 +29,12 @@ the driver keeps at most one plan active pool-wide, and per (src, dst)
 pair every rank issues chunk-major in global topo order — pairwise
 consistent by construction (checked at build time).
 
-Wire format: with ``build_plan(..., wire="mxfp8")``, ``"mxint8"`` or
-``"mxfp4"`` (driver config ``stream_wire_cast``) the remote edges of an
+Wire format: with ``build_plan(..., wire="mxfp8")``, ``"mxint8"``,
+``"mxfp4"`` or ``"mxfp6"`` (driver config ``stream_wire_cast``) the remote edges of an
 f32/bf16/f16 plan cross the link as block-scaled chunks — each chunk a
 self-contained buffer of that codec (``mxwire.wire_nbytes``), packed by the
 sender and combined by the codec's fused decode (``mxwire.mx8_axpby``,
-``mxwire.mxi8_axpby``, ``mxwire.mx4_axpby``) on arrival
+``mxwire.mxi8_axpby``, ``mxwire.mx4_axpby``, ``mxwire.mx6_axpby``) on arrival
 (docs/mxwire.md, "Plans").  The decision travels in the plan; ranks never
 consult their own configuration.
 """
@@ -52,7 +52,7 @@ from lzy_amd.utils.metrics import METRICS
 
 _LOG = logging.getLogger("lzy_amd.treeplan")
 
-WIRE_MODES = ("", "mxfp8", "mxint8", "mxfp4")
+WIRE_MODES = ("", "mxfp8", "mxint8", "mxfp4", "mxfp6")
 _WIRE_DTYPES = ("float32", "bfloat16", "float16")
 WIRE_MIN_NUMEL = 65536      # the transport's wire-cast threshold
 WIRE_CHUNK_QUANTUM = 256    # elements; chunk_elems of a wired plan
@@ -156,7 +156,7 @@ def build_plan(
     order inconsistency) — the caller then falls back to op-by-op
     execution.
 
-    ``wire="mxfp8"`` / ``"mxint8"`` / ``"mxfp4"`` asks for that block-scaled
+    ``wire="mxfp8"`` / ``"mxint8"`` / ``"mxfp4"`` / ``"mxfp6"`` asks for that block-scaled
     wire (docs/mxwire.md) on the plan's remote edges.  The driver alone decides: the plan carries
     the outcome in ``plan["wire"]`` and ranks follow it, never their own
     configuration.  Plans of another dtype or under the transport's size

@@ -45,12 +45,12 @@ class Config:
     # channels (reference: channel-manager + slots transports)
     channel_transport: str = "rccl"    # "rccl" | "ipc"
     channel_chunk_mb: int = 256        # chunk size for large-tensor transfers
-    channel_wire_cast: str = ""        # ""|fp16|bf16|mxfp8|mxint8|mxfp4|fp8e4m3|fp8e5m2: lossy wire format (8-bit: prefer mxfp8 or mxint8, block-scaled, every path; mxint8 has a third of the error unless blocks span a wide dynamic range; mxfp4 halves the bytes again at about 11% relative error per hop; plain fp8 is unscaled, RCCL-only)
+    channel_wire_cast: str = ""        # ""|fp16|bf16|mxfp8|mxint8|mxfp4|mxfp6|fp8e4m3|fp8e5m2: lossy wire format (8-bit: prefer mxfp8 or mxint8, block-scaled, every path; mxint8 has a third of the error unless blocks span a wide dynamic range; mxfp4 halves the bytes again at about 11% relative error per hop; mxfp6 keeps mxfp8's error at 24% fewer bytes; plain fp8 is unscaled, RCCL-only)
     channel_bundles: bool = True       # dict/list/tuple nests of tensors travel as packed bundles, not pickles (docs/bundles.md)
     bundle_wire_cast: str = ""         # ""|mxfp8: lossy wire format of bundles: f32/bf16/f16 leaves of >= 65536 elements cross ranks block-scaled FP8, other leaves exact (channel_wire_cast leaves bundles exact); the driver decides per transfer; same-rank consumers and the result cache see exact values
     stream_merge: bool = True         # fold pair_reduce trees into streamed plans
     stream_chunk_mb: int = 32          # chunk size for streamed tree plans (1 GiB shard -> 32 chunks; pipeline fill ~2 chunks per extra level)
-    stream_wire_cast: str = ""         # ""|mxfp8|mxint8|mxfp4: wire format of streamed tree plans (channel_wire_cast leaves plans exact); the driver decides per plan
+    stream_wire_cast: str = ""         # ""|mxfp8|mxint8|mxfp4|mxfp6: wire format of streamed tree plans (channel_wire_cast leaves plans exact); the driver decides per plan
     # HIP data-plane kernels
     hip_max_blocks: int = 0            # 0 -> kernel default grid cap
     op_streams: int = 4                # HIP streams per device for op overlap

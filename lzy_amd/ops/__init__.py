@@ -30,6 +30,7 @@ _MX_AXPBY_PACK = False
 _MX4 = False  # ... and lz_mx4_pack / lz_mx4_unpack / lz_mx4_axpby (MXFP4)
 # ... and lz_mx4_axpby_pack / lz_mx4_axpby2_pack (the forwarding node on MXFP4)
 _MX4_AXPBY_PACK = False
+_MX6 = False  # ... and lz_mx6_pack / lz_mx6_unpack / lz_mx6_axpby (MXFP6)
 _SEGCOPY = False  # ... and lz_segcopy (the packed-bundle gather/scatter)
 # bytes per tile of the segmented copy — LZ_SEG_TILE in hipops.hip
 SEGCOPY_TILE = 16384
@@ -219,6 +220,17 @@ def _try_load() -> Optional[ctypes.CDLL]:
         _MX4_AXPBY_PACK = True
     except AttributeError:
         _MX4_AXPBY_PACK = False
+    global _MX6
+    try:
+        lib.lz_mx6_pack.restype = ctypes.c_int
+        lib.lz_mx6_pack.argtypes = lib.lz_mx8_pack.argtypes
+        lib.lz_mx6_unpack.restype = ctypes.c_int
+        lib.lz_mx6_unpack.argtypes = lib.lz_mx8_unpack.argtypes
+        lib.lz_mx6_axpby.restype = ctypes.c_int
+        lib.lz_mx6_axpby.argtypes = lib.lz_mx8_axpby.argtypes
+        _MX6 = True
+    except AttributeError:
+        _MX6 = False
     global _SEGCOPY
     try:
         lib.lz_segcopy.restype = ctypes.c_int
@@ -368,6 +380,8 @@ def _mx_entry(op: str):
         present = _MX4_AXPBY_PACK if op.startswith("mx4_") else _MX_AXPBY_PACK
     elif op.startswith("mx4_"):
         present = _MX4
+    elif op.startswith("mx6_"):
+        present = _MX6
     else:
         present = _MX8_AXPBY if op == "mx8_axpby" else _MXI8
     if not present:
@@ -391,7 +405,15 @@ def mx4_nbytes(numel: int) -> int:
     return 17 * ((int(numel) + 31) // 32)
 
 
+def mx6_nbytes(numel: int) -> int:
+    """Wire bytes of ``numel`` elements in the block-scaled 6-bit format
+    (MXFP6, e2m3): 24 payload bytes + 1 scale byte per 32-element block."""
+    return 25 * ((int(numel) + 31) // 32)
+
+
 def _mx_nbytes(op: str, numel: int) -> int:
+    if op.startswith("mx6_"):
+        return mx6_nbytes(numel)
     return mx4_nbytes(numel) if op.startswith("mx4_") else mx8_nbytes(numel)
 
 
@@ -420,6 +442,12 @@ def mx4_pack(t, out=None):
     """:func:`mx8_pack` for the block-scaled FP4 (MXFP4) wire format
     (docs/mxwire.md): e2m1 nibbles, ``mx4_nbytes(t.numel())`` bytes."""
     return _mx_pack("mx4_pack", t, out)
+
+
+def mx6_pack(t, out=None):
+    """:func:`mx8_pack` for the block-scaled FP6 (MXFP6) wire format
+    (docs/mxwire.md): 6-bit e2m3 codes, ``mx6_nbytes(t.numel())`` bytes."""
+    return _mx_pack("mx6_pack", t, out)
 
 
 def _mx_pack(op: str, t, out):
@@ -466,6 +494,12 @@ def mx4_unpack(buf, numel_or_shape, dtype, out=None):
     """:func:`mx8_unpack` for an MXFP4 wire buffer
     (``uint8[mx4_nbytes(numel)]``)."""
     return _mx_unpack("mx4_unpack", buf, numel_or_shape, dtype, out)
+
+
+def mx6_unpack(buf, numel_or_shape, dtype, out=None):
+    """:func:`mx8_unpack` for an MXFP6 wire buffer
+    (``uint8[mx6_nbytes(numel)]``)."""
+    return _mx_unpack("mx6_unpack", buf, numel_or_shape, dtype, out)
 
 
 def _mx_unpack(op: str, buf, numel_or_shape, dtype, out):
@@ -531,6 +565,13 @@ def mx4_axpby(a, wire, alpha: float = 1.0, beta: float = 1.0, dst=None):
     MXFP4 buffer (``uint8[mx4_nbytes(a.numel())]``), everything else is the
     same."""
     return _mx_axpby("mx4_axpby", a, wire, alpha, beta, dst)
+
+
+def mx6_axpby(a, wire, alpha: float = 1.0, beta: float = 1.0, dst=None):
+    """:func:`mx8_axpby` with the MXFP6 decode fused in: ``wire`` is an
+    MXFP6 buffer (``uint8[mx6_nbytes(a.numel())]``), everything else is the
+    same."""
+    return _mx_axpby("mx6_axpby", a, wire, alpha, beta, dst)
 
 
 def _mx_axpby(op: str, a, wire, alpha, beta, dst):

@@ -2042,6 +2042,385 @@ extern "C" hipError_t lz_mx4_axpby2_pack(const void* a, const void* b, int src_d
 }
 
 // ---------------------------------------------------------------------------
+// mx6: the block-scaled FP6 codec (OCP MXFP6 with e2m3 elements,
+// docs/mxwire.md "MXFP6").
+//
+// Every 32 elements share one E8M0 scale byte; an element is a 6-bit e2m3
+// code (sign, 2 exponent bits of bias 1, 3 mantissa bits; magnitudes m/8 and
+// (1 + m/8) * 2^(e-1), 7.5 at most, no NaN or Inf).  Element i of a block is
+// bits [6i, 6i+6) of the block's 24 payload bytes read as one little-endian
+// integer.  Wire buffer for n elements, nblk = ceil(n/32): payload bytes
+// [0, 24*nblk), then nblk scale bytes: 25/32 B per element.  A block with a
+// NaN is scale byte 0xff over an all-zero payload.
+//
+// Work item = 16 consecutive elements ("half"), which are exactly three
+// payload dwords: the two lanes of an aligned pair own one block, a wave 32
+// blocks (768 contiguous payload bytes, 32 scale bytes).  A lane's elements
+// arrive as two 16 B loads (16-bit sources) or four (f32), all issued before
+// the first is consumed; its payload moves as one 12 B access.
+//
+// No FP6 convert is used: gfx950's want a whole block in one lane.  e2m3 is a
+// sub-grid of e4m3 instead: for |y| <= 7.5 the e2m3 magnitude code of y is
+// the low five bits of the e4m3fn code of y/64 (both grids are m * 2^-9 below
+// 2^-6 and (1 + m/8) * 2^(e-7) for exponent field 1..3, so RNE and its ties
+// coincide and bits 5..6 of the e4m3 byte are zero).  Encode: v_ldexp_f32 by
+// 121-b (exact; 2^(121-b) itself is no normal fp32 for b > 247), v_med3_f32
+// to +-7.5/64 (moves +-Inf only), v_cvt_pk_fp8_f32, sign bit 7 -> bit 5, four
+// 8-bit fields squeezed into 24 bits.  Decode is the inverse and ends in
+// v_ldexp_f32 by b-121, exact for every b but the overflow of b = 254.
+//
+// ALIGNED: 16 B accesses to the tensors and 4 B-aligned accesses to the wire.
+// Element-aligned views and the tail take the guarded path of the same
+// kernels.  Compiled without packed fp32 VALU ops, as the mxi8 kernels are.
+// ---------------------------------------------------------------------------
+
+struct alignas(4) LzVec12 { uint32_t w[3]; };
+
+// scale byte of a block from the raw bits of its finite amax (>= 0): the
+// smallest 2^(b-127) with amax / 2^(b-127) <= 7.5 = 1.875 * 2^2, i.e. E - 2,
+// one more from m = 0x700001 on (adding 0x0fffff carries into the exponent
+// exactly then), not below 0.  FLT_MAX gives 253.
+__device__ __forceinline__ uint32_t lz_mx6_scale_byte(uint32_t amax_bits) {
+    const uint32_t t = (amax_bits + 0x0fffffu) >> 23;
+    return t > 2u ? t - 2u : 0u;
+}
+
+// a lane's 16 elements as fp32.  FULL: all 16 lie inside [0, n) and src + e0
+// is 16 B-aligned; otherwise guarded, zeros past n.
+template <typename T, bool FULL>
+__device__ __forceinline__ void lz_mx6_load(const T* src, int64_t e0, int64_t n,
+                                            float (&f)[16]) {
+    constexpr int V = 16;
+    T x[V];
+    if (FULL) {
+        LzVec16 q[sizeof(T) * V / 16];
+        const LzVec16* p = reinterpret_cast<const LzVec16*>(src + e0);
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(T) * V / 16); ++k) q[k] = p[k];
+        __builtin_memcpy(x, q, sizeof(x));
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            x[k] = (e0 + k < n) ? src[e0 + k] : lz_from_float<T>(0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) f[k] = lz_to_float<T>(x[k]);
+}
+
+// 4 floats -> their 4 codes in 24 bits (element k at bits [6k, 6k+6)).  The
+// convert rounds to nearest even, keeps the sign of a zero result and sees
+// nothing beyond +-7.5/64 (a NaN element leaves med3 as some number: its
+// block's payload is overridden by the caller).
+__device__ __forceinline__ uint32_t lz_mx6_encode4(const float* f, int e) {
+    constexpr float LIM = 0.1171875f;  // 7.5 / 64
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        v[k] = __builtin_amdgcn_fmed3f(__builtin_ldexpf(f[k], e), -LIM, LIM);
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w, true);
+    const uint32_t u = (uint32_t)w;
+    // per byte: magnitude bits 0..4 stay, sign bit 7 moves to bit 5
+    const uint32_t c = (u & 0x1f1f1f1fu) | ((u >> 2) & 0x20202020u);
+    // bytes 1 and 3 close up to their lower neighbours, then the upper pair
+    // to the lower one
+    const uint32_t t = (c & 0x003f003fu) | ((c >> 2) & 0x0fc00fc0u);
+    return (t & 0xfffu) | ((t >> 4) & 0xfff000u);
+}
+
+// 24 bits of codes -> 4 fp32 values e2m3(q) / 64, the sign of a zero kept
+__device__ __forceinline__ void lz_mx6_decode4(uint32_t s, float* x) {
+    const uint32_t t = (s & 0xfffu) | ((s << 4) & 0x0fff0000u);
+    const uint32_t c = (t & 0x003f003fu) | ((t << 2) & 0x3f003f00u);
+    const uint32_t u = (c & 0x1f1f1f1fu) | ((c << 2) & 0x80808080u);
+    lz_f32x2 p = __builtin_amdgcn_cvt_pk_f32_fp8((int)u, false);
+    x[0] = p.x; x[1] = p.y;
+    p = __builtin_amdgcn_cvt_pk_f32_fp8((int)u, true);
+    x[2] = p.x; x[3] = p.y;
+}
+
+// quantize and store one half (16 elements of lane `lane`, half h); every
+// lane of the wave calls this together (DPP).  FULL: all 64 halves of the
+// wave are inside the tensor.
+template <bool ALIGNED, bool FULL>
+__device__ __forceinline__ void lz_mx6_emit(const float (&f)[16], int64_t h, int lane,
+                                            int64_t nhalves, int64_t nblk,
+                                            uint8_t* __restrict__ dst,
+                                            uint8_t* __restrict__ scales) {
+    // the finite amax and the has-NaN flag in one key, as in lz_mx4_emit
+    int32_t tmax = 0x00800000;
+    uint32_t umax = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const uint32_t a = __float_as_uint(f[k]) & 0x7fffffffu;
+        const int32_t t = (int32_t)(a + 0x00800000u);
+        umax = a > umax ? a : umax;
+        tmax = t > tmax ? t : tmax;
+    }
+    uint32_t key = umax > 0x7f800000u ? 0xffffffffu : (uint32_t)tmax - 0x00800000u;
+    // the two lanes of a block: one DPP step
+    const uint32_t o = lz_dpp<LZ_DPP_QUAD_XOR1>(key);
+    key = o > key ? o : key;
+    const bool nan = key > 0x7f7fffffu;
+    const uint32_t b = nan ? 0xffu : lz_mx6_scale_byte(key);
+
+    const int e = 121 - (int)b;
+    const uint32_t s0 = lz_mx6_encode4(&f[0], e), s1 = lz_mx6_encode4(&f[4], e);
+    const uint32_t s2 = lz_mx6_encode4(&f[8], e), s3 = lz_mx6_encode4(&f[12], e);
+    LzVec12 pv;
+    pv.w[0] = nan ? 0u : (s0 | (s1 << 24));
+    pv.w[1] = nan ? 0u : ((s1 >> 8) | (s2 << 16));
+    pv.w[2] = nan ? 0u : ((s2 >> 16) | (s3 << 8));
+
+    // the scale bytes of 4 blocks (8 lanes) gathered into the first of the
+    // lanes: a wave's 32 scale bytes leave as 8 adjacent dword stores
+    uint32_t sw = b;
+    sw |= lz_dpp<LZ_DPP_ROW_SHL(2)>(b) << 8;
+    sw |= lz_dpp<LZ_DPP_ROW_SHL(4)>(b) << 16;
+    sw |= lz_dpp<LZ_DPP_ROW_SHL(6)>(b) << 24;
+
+    if (FULL || h < nhalves) {
+        if (ALIGNED) {
+            *reinterpret_cast<LzVec12*>(dst + h * 12) = pv;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 12; ++k)
+                dst[h * 12 + k] = (uint8_t)(pv.w[k >> 2] >> (8 * (k & 3)));
+        }
+        if ((lane & 7) == 0) {
+            const int64_t blk = h >> 1;  // multiple of 4
+            if (ALIGNED && (FULL || blk + 4 <= nblk)) {
+                *reinterpret_cast<uint32_t*>(scales + blk) = sw;
+            } else {
+                for (int k = 0; k < 4 && blk + k < nblk; ++k)
+                    scales[blk + k] = (uint8_t)(sw >> (8 * k));
+            }
+        }
+    }
+}
+
+// h0, the half of the wave's lane 0, and every branch on it are wave-uniform:
+// the cross-lane steps always run with all 64 lanes, and a lane whose half
+// lies past the tensor encodes zeros and stores nothing.
+template <typename T, bool ALIGNED>
+__global__ void __launch_bounds__(LZ_BLOCK) LZ_NO_PK_F32
+mx6_pack_kernel(const T* __restrict__ src, uint8_t* __restrict__ dst, int64_t n) {
+    const int64_t nblk = (n + 31) >> 5;
+    const int64_t nhalves = nblk * 2;
+    uint8_t* __restrict__ scales = dst + nblk * 24;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+
+    for (int64_t h0 = (int64_t)blockIdx.x * blockDim.x + wave * 64; h0 < nhalves;
+         h0 += stride) {
+        const int64_t h = h0 + lane;
+        float f[16];
+        if (ALIGNED && (h0 + 64) * 16 <= n) {
+            lz_mx6_load<T, true>(src, h * 16, n, f);
+            lz_mx6_emit<true, true>(f, h, lane, nhalves, nblk, dst, scales);
+        } else {
+            lz_mx6_load<T, false>(src, h * 16, n, f);
+            lz_mx6_emit<ALIGNED, false>(f, h, lane, nhalves, nblk, dst, scales);
+        }
+    }
+}
+
+// decode one half and store it, or (COMBINE) its combine with the 16
+// elements fa of the accumulator: fmaf(a, alpha, x * beta), x in fp32.
+// FULL: all 16 elements lie in [0, n) and dst + e0 is 16 B-aligned.
+template <typename DstT, bool FULL, bool COMBINE>
+__device__ __forceinline__ void lz_mx6_dec_store(const LzVec12& pv, uint32_t b,
+                                                 const float (&fa)[16], DstT* dst,
+                                                 int64_t e0, int64_t n, float alpha,
+                                                 float beta) {
+    constexpr int V = 16;
+    float x[V];
+    lz_mx6_decode4(pv.w[0] & 0xffffffu, &x[0]);
+    lz_mx6_decode4((pv.w[0] >> 24) | ((pv.w[1] & 0xffffu) << 8), &x[4]);
+    lz_mx6_decode4((pv.w[1] >> 16) | ((pv.w[2] & 0xffu) << 16), &x[8]);
+    lz_mx6_decode4(pv.w[2] >> 8, &x[12]);
+    const int e = (int)b - 121;
+    DstT y[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        float r = __builtin_ldexpf(x[k], e);
+        r = b == 0xffu ? __uint_as_float(0x7fc00000u) : r;
+        if constexpr (COMBINE) {
+            r = fmaf(fa[k], alpha, r * beta);
+            // the contract rounds to fp32, then to the 16-bit type: keep the
+            // FMA and the f16 convert from fusing into one single-rounding
+            // v_fma_mixlo_f16
+#if defined(__HIP_DEVICE_COMPILE__)
+            if constexpr (std::is_same<DstT, __half>::value) asm("" : "+v"(r));
+#endif
+        }
+        y[k] = lz_from_float<DstT>(r);
+    }
+    if (FULL) {
+        LzVec16 q[sizeof(DstT) * V / 16];
+        __builtin_memcpy(q, y, sizeof(y));
+        LzVec16* p = reinterpret_cast<LzVec16*>(dst + e0);
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(DstT) * V / 16); ++k) p[k] = q[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+            if (e0 + k < n) dst[e0 + k] = y[k];
+    }
+}
+
+// mx6_unpack (COMBINE false: a unused) and mx6_axpby share this kernel: three
+// payload dwords and the block's scale byte per lane, 16 elements out,
+// nothing crosses lanes.  Every load of a half (payload, scale byte and the
+// two or four 16 B loads of `a`) issues before the first store.  `a` and
+// `dst` may be the same pointer (a lane reads its 16 elements before it
+// writes them), so neither is __restrict__.
+template <typename SrcT, typename DstT, bool ALIGNED, bool COMBINE>
+__global__ void __launch_bounds__(LZ_BLOCK) LZ_NO_PK_F32
+mx6_decode_kernel(const SrcT* a, const uint8_t* __restrict__ wire, DstT* dst, int64_t n,
+                  float alpha, float beta) {
+    const int64_t nblk = (n + 31) >> 5;
+    const int64_t nhalves = nblk * 2;
+    const uint8_t* __restrict__ scales = wire + nblk * 24;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+
+    for (int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < nhalves;
+         h += stride) {
+        const int64_t e0 = h * 16;
+        if (e0 >= n) continue;  // padded second half of the last block
+        // the 12 payload bytes of half h exist for every h < 2*nblk
+        LzVec12 pv;
+        if (ALIGNED) {
+            pv = *reinterpret_cast<const LzVec12*>(wire + h * 12);
+        } else {
+            pv.w[0] = pv.w[1] = pv.w[2] = 0;
+#pragma unroll
+            for (int k = 0; k < 12; ++k)
+                pv.w[k >> 2] |= (uint32_t)wire[h * 12 + k] << (8 * (k & 3));
+        }
+        const uint32_t b = scales[h >> 1];
+        float fa[16] = {};
+        if (ALIGNED && e0 + 16 <= n) {
+            if constexpr (COMBINE) lz_mx6_load<SrcT, true>(a, e0, n, fa);
+            lz_mx6_dec_store<DstT, true, COMBINE>(pv, b, fa, dst, e0, n, alpha, beta);
+        } else {
+            if constexpr (COMBINE) lz_mx6_load<SrcT, false>(a, e0, n, fa);
+            lz_mx6_dec_store<DstT, false, COMBINE>(pv, b, fa, dst, e0, n, alpha, beta);
+        }
+    }
+}
+
+static inline int lz_mx6_grid(int64_t n) {
+    int64_t nhalves = ((n + 31) >> 5) * 2;
+    int64_t want = (nhalves + LZ_BLOCK - 1) / LZ_BLOCK;
+    return (int)(want < 1 ? 1 : (want > g_max_blocks ? g_max_blocks : want));
+}
+
+// src: n elements of src_dtype (f32/f16/bf16); dst_u8: 25*ceil(n/32) bytes
+extern "C" hipError_t lz_mx6_pack(const void* src, int src_dtype, void* dst_u8,
+                                  int64_t n, void* stream) {
+    if (!lz_mx_float_dtype(src_dtype) || n < 0) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    const int blocks = lz_mx6_grid(n);
+    const bool aligned = (((uintptr_t)src & 15) == 0) && (((uintptr_t)dst_u8 & 3) == 0);
+#define LZ_MX6P_CASE(code, T)                                                   \
+    case code:                                                                  \
+        if (aligned)                                                            \
+            hipLaunchKernelGGL((mx6_pack_kernel<T, true>), dim3(blocks),        \
+                               dim3(LZ_BLOCK), 0, s, (const T*)src,             \
+                               (uint8_t*)dst_u8, n);                            \
+        else                                                                    \
+            hipLaunchKernelGGL((mx6_pack_kernel<T, false>), dim3(blocks),       \
+                               dim3(LZ_BLOCK), 0, s, (const T*)src,             \
+                               (uint8_t*)dst_u8, n);                            \
+        break;
+    switch (src_dtype) {
+        LZ_MX6P_CASE(LZ_F32, float)
+        LZ_MX6P_CASE(LZ_F16, __half)
+        LZ_MX6P_CASE(LZ_BF16, __hip_bfloat16)
+        default: return hipErrorInvalidValue;
+    }
+#undef LZ_MX6P_CASE
+    return hipGetLastError();
+}
+
+template <typename SrcT, typename DstT, bool COMBINE>
+static void lz_mx6_decode_launch(const void* a, const void* wire_u8, void* dst, int64_t n,
+                                 float alpha, float beta, bool aligned, hipStream_t s) {
+    const int blocks = lz_mx6_grid(n);
+    if (aligned)
+        hipLaunchKernelGGL((mx6_decode_kernel<SrcT, DstT, true, COMBINE>), dim3(blocks),
+                           dim3(LZ_BLOCK), 0, s, (const SrcT*)a, (const uint8_t*)wire_u8,
+                           (DstT*)dst, n, alpha, beta);
+    else
+        hipLaunchKernelGGL((mx6_decode_kernel<SrcT, DstT, false, COMBINE>), dim3(blocks),
+                           dim3(LZ_BLOCK), 0, s, (const SrcT*)a, (const uint8_t*)wire_u8,
+                           (DstT*)dst, n, alpha, beta);
+}
+
+// src_u8: 25*ceil(n/32) bytes; dst: n elements of dst_dtype (f32/f16/bf16)
+extern "C" hipError_t lz_mx6_unpack(const void* src_u8, void* dst, int dst_dtype,
+                                    int64_t n, void* stream) {
+    if (!lz_mx_float_dtype(dst_dtype) || n < 0) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    const bool aligned = (((uintptr_t)src_u8 & 3) == 0) && (((uintptr_t)dst & 15) == 0);
+    switch (dst_dtype) {
+        case LZ_F32:
+            lz_mx6_decode_launch<float, float, false>(nullptr, src_u8, dst, n, 0.f, 0.f,
+                                                      aligned, s);
+            break;
+        case LZ_F16:
+            lz_mx6_decode_launch<__half, __half, false>(nullptr, src_u8, dst, n, 0.f, 0.f,
+                                                        aligned, s);
+            break;
+        default:
+            lz_mx6_decode_launch<__hip_bfloat16, __hip_bfloat16, false>(
+                nullptr, src_u8, dst, n, 0.f, 0.f, aligned, s);
+            break;
+    }
+    return hipGetLastError();
+}
+
+// a: n elements of a_dtype; wire_u8: 25*ceil(n/32) bytes; dst: n elements of
+// dst_dtype (both f32/f16/bf16).  dst == a is allowed, partial overlap is not.
+extern "C" hipError_t lz_mx6_axpby(const void* a, int a_dtype, const void* wire_u8,
+                                   void* dst, int dst_dtype, int64_t n, float alpha,
+                                   float beta, void* stream) {
+    if (!lz_mx_float_dtype(a_dtype) || !lz_mx_float_dtype(dst_dtype) || n < 0)
+        return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    const bool aligned = (((uintptr_t)a & 15) == 0) && (((uintptr_t)dst & 15) == 0) &&
+                         (((uintptr_t)wire_u8 & 3) == 0);
+#define LZ_MX6A_DST(SrcT, code, DstT)                                           \
+    case code:                                                                  \
+        lz_mx6_decode_launch<SrcT, DstT, true>(a, wire_u8, dst, n, alpha, beta, \
+                                               aligned, s);                     \
+        break;
+#define LZ_MX6A_SRC(scode, SrcT)                                                \
+    case scode:                                                                 \
+        switch (dst_dtype) {                                                    \
+            LZ_MX6A_DST(SrcT, LZ_F32, float)                                    \
+            LZ_MX6A_DST(SrcT, LZ_F16, __half)                                   \
+            default:                                                            \
+                LZ_MX6A_DST(SrcT, LZ_BF16, __hip_bfloat16)                      \
+        }                                                                       \
+        break;
+    switch (a_dtype) {
+        LZ_MX6A_SRC(LZ_F32, float)
+        LZ_MX6A_SRC(LZ_F16, __half)
+        default:
+            LZ_MX6A_SRC(LZ_BF16, __hip_bfloat16)
+    }
+#undef LZ_MX6A_SRC
+#undef LZ_MX6A_DST
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // mx8_axpby_pack / mx8_axpby2_pack: the step of a merge-tree node that
 // forwards (docs/mxwire.md, "Forwarding nodes"), in one pass:
 //   dst      = cast(alpha*a + beta*x)   x = decode(wire_in), or a plain b

@@ -1214,10 +1214,10 @@ class _DriverScheduler:
         # wire format of streamed plans; the driver decides, the plan
         # carries it to the ranks (channel_wire_cast leaves plans exact)
         self._stream_wire = str(getattr(cfg, "stream_wire_cast", "") or "")
-        if self._stream_wire not in ("", "mxfp8", "mxint8", "mxfp4"):
+        if self._stream_wire not in ("", "mxfp8", "mxint8", "mxfp4", "mxfp6"):
             raise ValueError(
-                f"stream_wire_cast must be \"\", \"mxfp8\", \"mxint8\" or "
-                f"\"mxfp4\", got {self._stream_wire!r}"
+                f"stream_wire_cast must be \"\", \"mxfp8\", \"mxint8\", "
+                f"\"mxfp4\" or \"mxfp6\", got {self._stream_wire!r}"
             )
         # wire format of tensor bundles (docs/bundles.md): again the
         # driver's decision, carried by the transfer items
