@@ -435,6 +435,12 @@ class Transport:
         ``offset_chunks``/``into`` resume into an existing buffer that
         already holds the first ``offset_chunks`` chunks (for a wired
         bundle: of the WIRE buffer).  ``wire``: see :meth:`send_ops`."""
+        if into is not None:
+            # the collective writes it by pointer: what ops remembers of its
+            # contents (a scale_shift record) no longer holds
+            from lzy_amd import ops as _ops
+
+            _ops.forget(into)
         if meta.kind == KIND_BUNDLE:
             # the sender's packed uint8 buffer over the tensor path (same
             # chunking, staging and tag rules, never cast); the leaves are

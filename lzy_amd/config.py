@@ -53,6 +53,7 @@ class Config:
     stream_wire_cast: str = ""         # ""|mxfp8|mxint8|mxfp4|mxfp6: wire format of streamed tree plans (channel_wire_cast leaves plans exact); the driver decides per plan
     # HIP data-plane kernels
     hip_max_blocks: int = 0            # 0 -> kernel default grid cap
+    hip_emit: bool = True              # scale_shift emits its output's mfma digest and |x| moments in the same pass; device_checksum / stats(use_abs) / abs_mean of that tensor then read nothing (docs/api.md, "scale_shift records")
     op_streams: int = 4                # HIP streams per device for op overlap
     # scheduler / pool
     dispatch_workers: int = 0          # 0 -> auto (LocalRuntime thread pool size)

@@ -42,6 +42,12 @@ SEGCODEC_TILE_ELEMS = 8192
 SEGCODEC_RAW = 0
 SEGCODEC_ENCODE = 1
 SEGCODEC_DECODE = 4
+# ... and lz_scale_shift_emit / lz_checksum_mfma_blocks / lz_get_max_blocks
+# (scale_shift that also emits its output's digest and |x| moments)
+_EMIT = False
+# times a consumer answered from a scale_shift record instead of a kernel
+# pass over the tensor (tests read it; nothing else depends on it)
+_emit_hits = 0
 
 
 def _try_load() -> Optional[ctypes.CDLL]:
@@ -259,6 +265,21 @@ def _try_load() -> Optional[ctypes.CDLL]:
             lib.lz_segcodec_tile_elems() == SEGCODEC_TILE_ELEMS
     except AttributeError:
         _SEGCODEC = False
+    global _EMIT
+    try:
+        lib.lz_scale_shift_emit.restype = ctypes.c_int
+        lib.lz_scale_shift_emit.argtypes = [
+            ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+            ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_void_p,
+        ]
+        lib.lz_checksum_mfma_blocks.restype = ctypes.c_int
+        lib.lz_checksum_mfma_blocks.argtypes = [ctypes.c_int64]
+        lib.lz_get_max_blocks.restype = ctypes.c_int
+        lib.lz_get_max_blocks.argtypes = []
+        _EMIT = True
+    except AttributeError:
+        _EMIT = False
     lib.lz_error_name.restype = ctypes.c_char_p
     lib.lz_error_name.argtypes = [ctypes.c_int]
     lib.lz_set_max_blocks.restype = None
@@ -333,6 +354,86 @@ def _check_dst(op: str, dst, numel: int, shape=None) -> None:
         raise ValueError(
             f"{op}: dst has shape {tuple(dst.shape)}, expected {tuple(shape)}"
         )
+    forget(dst)  # every caller is about to write dst by pointer
+
+
+# ---------------------------------------------------------------------------
+# scale_shift records: the digest and |x| moments of a fresh scale_shift
+# output, computed by the kernel that wrote it (docs/api.md, "scale_shift
+# records").  The record is an attribute of the returned tensor OBJECT — not
+# a table keyed by address — so it dies with the object, and a view, a
+# detach() or a copy has none.
+# ---------------------------------------------------------------------------
+
+_EMIT_ATTR = "_lz_emit"
+_EMIT_MIN_BYTES = 64 << 10  # where device_checksum(method="auto") picks mfma
+
+
+class _EmitRecord:
+    __slots__ = ("buf", "version", "ptr", "numel", "dtype", "blocks")
+
+    def __init__(self, buf, t, blocks: int) -> None:
+        self.buf = buf  # int64[3] on t's device: digest, then two f64 moments
+        self.version = t._version
+        self.ptr = t.data_ptr()
+        self.numel = t.numel()
+        self.dtype = t.dtype
+        self.blocks = blocks  # grid of the emitting kernel = of lz_checksum_mfma
+
+    def __reduce__(self):
+        # a pickled or deep-copied tensor is another tensor: it gets no record
+        return (type(None), ())
+
+
+def _emit_enabled() -> bool:
+    from lzy_amd.config import get_config
+
+    return _EMIT and bool(get_config().hip_emit)
+
+
+def _emit_record(t) -> Optional[_EmitRecord]:
+    """The record of ``t`` if it still describes ``t``'s bytes: same object,
+    contiguous, unmodified since (torch's in-place ops bump ``_version``, our
+    own pointer writes call :func:`forget`), same storage window and dtype,
+    and the grid ``lz_checksum_mfma`` would use now is the recorded one (the
+    digest depends on it)."""
+    rec = getattr(t, "__dict__", {}).get(_EMIT_ATTR)
+    if rec is None or not _emit_enabled():
+        return None
+    if not (
+        t.is_contiguous()
+        and t._version == rec.version
+        and t.data_ptr() == rec.ptr
+        and t.numel() == rec.numel
+        and t.dtype == rec.dtype
+        and t.device == rec.buf.device
+        and _lib.lz_checksum_mfma_blocks(rec.numel * t.element_size()) == rec.blocks
+    ):
+        return None
+    global _emit_hits
+    _emit_hits += 1
+    return rec
+
+
+def forget(t) -> None:
+    """Drop what ``ops`` remembers about ``t``'s contents.  Call it before
+    writing into an existing tensor through its raw pointer (a kernel of
+    your own, a collective receiving into it): every ``ops`` wrapper that
+    does so calls it, and torch's own in-place ops need nothing.
+
+    Besides dropping ``t``'s own record this bumps ``t``'s version counter,
+    which a view, its base and a ``detach()`` share — so a record held by
+    another tensor object over the same memory goes stale too."""
+    d = getattr(t, "__dict__", None)
+    if d:
+        d.pop(_EMIT_ATTR, None)
+    if _EMIT:
+        import torch
+
+        try:
+            torch.autograd.graph.increment_version(t)
+        except (RuntimeError, AttributeError):
+            pass  # an inference tensor has no version counter (and no record)
 
 
 def cast_copy(src, dst) -> None:
@@ -529,6 +630,8 @@ def _mx_unpack(op: str, buf, numel_or_shape, dtype, out):
         raise ValueError(
             f"{op}: out must be a contiguous device {dtype}[{n}]"
         )
+    else:
+        forget(out)
     _check(
         fn(
             ctypes.c_void_p(buf.data_ptr()),
@@ -964,6 +1067,8 @@ def unpack_tensors(buf, offsets, shapes, dtypes, out=None):
                 f"unpack_tensors: out tensor is {o.dtype}{tuple(o.shape)}, "
                 f"expected {dt}{s}"
             )
+    for o in out:
+        forget(o)
     lib = _require_segcopy()
     base = buf.data_ptr()
     _segcopy_launch(
@@ -1065,6 +1170,7 @@ def _check_packed_out(op: str, out, total: int, align: int, device) -> None:
         raise ValueError(f"{op}: out is on another device")
     if out.data_ptr() % align:
         raise ValueError(f"{op}: out must be {align} B-aligned")
+    forget(out)
 
 
 def _aligned_empty(total: int, align: int, device):
@@ -1237,12 +1343,20 @@ def device_checksum(t, method: str = "auto") -> int:
     default for buffers >= 64 KiB — VALU stays free, bandwidth-bound),
     "valu" is the splitmix64 kernel, "auto" picks by size.  The two
     digests are different hash functions (both stable across runs).
+
+    A fresh ``scale_shift`` output carries its mfma digest already
+    (docs/api.md, "scale_shift records"): "auto" and "mfma" then fetch
+    those 8 bytes and read nothing else.
     """
     import torch
 
     lib = _require_native()
     if not t.is_cuda:
         raise ValueError("device_checksum requires a device tensor")
+    if method in ("auto", "mfma"):
+        rec = _emit_record(t)
+        if rec is not None:
+            return int(rec.buf[0].item()) & 0xFFFFFFFFFFFFFFFF
     flat = t.detach().contiguous().view(torch.uint8) if t.dtype != torch.uint8 \
         else t.detach().contiguous()
     nbytes = flat.numel() * flat.element_size()
@@ -1263,12 +1377,20 @@ def device_checksum(t, method: str = "auto") -> int:
 
 def stats(t, use_abs: bool = False):
     """One-pass (sum, sumsq) — or (sum|x|, sumsq) — of a device tensor.
-    Returns a device float64[2] tensor; no host sync."""
+    Returns a device float64[2] tensor; no host sync.
+
+    With ``use_abs`` a fresh ``scale_shift`` output answers from its record
+    (docs/api.md, "scale_shift records"): a device copy of the two sums the
+    producing kernel left, no pass over the tensor."""
     import torch
 
     lib = _require_native()
     if not t.is_cuda:
         raise ValueError("stats requires a device tensor")
+    if use_abs:
+        rec = _emit_record(t)
+        if rec is not None:
+            return rec.buf[1:3].view(torch.float64).clone()
     flat = t.detach().contiguous()
     out = torch.empty(2, dtype=torch.float64, device=t.device)
     _check(
@@ -1357,9 +1479,51 @@ def normalize(src, dst=None, eps: float = 1e-6):
     return dst
 
 
+def _scale_shift_emit(lib, s, a: float, b: float, dst) -> bool:
+    """Fill the fresh ``dst`` with the emitting kernel and attach the record;
+    False when the case is not the kernel's (the caller runs the plain one)."""
+    import torch
+
+    nbytes = dst.numel() * dst.element_size()
+    if not (
+        nbytes >= _EMIT_MIN_BYTES
+        and s.element_size() == dst.element_size()
+        and s.dtype in (torch.float32, torch.float16, torch.bfloat16)
+        and dst.is_contiguous()
+        and (s.data_ptr() | dst.data_ptr()) % 16 == 0
+        and not dst.is_inference()
+        and _emit_enabled()
+    ):
+        return False
+    buf = torch.empty(3, dtype=torch.int64, device=dst.device)
+    err = lib.lz_scale_shift_emit(
+        ctypes.c_void_p(s.data_ptr()),
+        _dtype_code(s.dtype),
+        ctypes.c_void_p(dst.data_ptr()),
+        _dtype_code(dst.dtype),
+        s.numel(),
+        ctypes.c_float(a),
+        ctypes.c_float(b),
+        ctypes.c_void_p(buf.data_ptr()),
+        ctypes.c_void_p(buf.data_ptr() + 8),
+        ctypes.c_void_p(_current_stream_ptr()),
+    )
+    if err == 1:  # hipErrorInvalidValue: a pair or alignment it does not take
+        return False
+    _check(err)
+    setattr(dst, _EMIT_ATTR,
+            _EmitRecord(buf, dst, lib.lz_checksum_mfma_blocks(nbytes)))
+    return True
+
+
 def scale_shift(src, a: float, b: float, dst=None):
     """dst = src * a + b (fused single-FMA elementwise; in-place when
-    dst is src)."""
+    dst is src).
+
+    A new output (``dst=None``) of a same-width f32/f16/bf16 pair and at
+    least 64 KiB comes from the emitting kernel, which leaves the output's
+    mfma digest and |x| moments in a record on the returned tensor
+    (docs/api.md, "scale_shift records"); the values written are the same."""
     import torch
 
     lib = _require_native()
@@ -1368,6 +1532,8 @@ def scale_shift(src, a: float, b: float, dst=None):
     s = src.detach().contiguous()
     if dst is None:
         dst = torch.empty_like(s)
+        if _scale_shift_emit(lib, s, a, b, dst):
+            return dst
     else:
         _check_dst("scale_shift", dst, s.numel())
     _check(
@@ -1462,6 +1628,7 @@ def fill_pattern(t, seed: int = 0, mask16: int = 0) -> None:
         raise ValueError("fill_pattern requires a device tensor")
     if not t.is_contiguous():
         raise ValueError("fill_pattern: tensor must be contiguous")
+    forget(t)
     flat = t.detach()
     nbytes = flat.numel() * flat.element_size()
     if mask16:

@@ -745,6 +745,68 @@ extern "C" hipError_t lz_checksum(const void* data, int64_t nbytes,
 typedef __attribute__((ext_vector_type(4))) int lz_i32x4;
 typedef __attribute__((ext_vector_type(16))) int lz_i32x16;
 
+// The pieces of the digest are device functions: scale_shift_emit_kernel
+// (below) produces the same digest from the bytes it has just computed, so
+// the two kernels share every step that decides the value.
+
+// A operand: fixed dense pseudo-random bytes per lane (4 dwords)
+__device__ __forceinline__ lz_i32x4 lz_mfma_a_frag(int lane) {
+    lz_i32x4 a_frag;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        a_frag[r] = (int)(uint32_t)(splitmix64(0x5EEDULL * 131 + lane * 4 + r) | 0x01010101u);
+    return a_frag;
+}
+
+// acc += A · (b ^ salt(t)): one 1 KiB tile, b = this lane's 16 bytes of it
+__device__ __forceinline__ lz_i32x16 lz_mfma_mix_tile(lz_i32x4 a_frag, lz_i32x4 b,
+                                                      int64_t t, lz_i32x16 acc) {
+    const uint64_t s = splitmix64((uint64_t)t);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        b[r] ^= (int)(uint32_t)(s >> ((r * 13) & 31));
+    return __builtin_amdgcn_mfma_i32_32x32x32_i8(a_frag, b, acc, 0, 0, 0);
+}
+
+// fold accumulators with position salts
+__device__ __forceinline__ uint64_t lz_mfma_fold(lz_i32x16 acc, int lane) {
+    uint64_t h = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        h += splitmix64((uint32_t)acc[r] ^ splitmix64((uint64_t)(lane * 16 + r)));
+    return h;
+}
+
+// tail (< 1 KiB) + length: one thread via the scalar mix
+__device__ __forceinline__ uint64_t lz_mfma_tail(const uint8_t* data, int64_t nbytes) {
+    const int64_t ntiles = nbytes >> 10;
+    uint64_t h = 0;
+    const uint8_t* p = data + (ntiles << 10);
+    int64_t rem = nbytes - (ntiles << 10);
+    const uint64_t* words = reinterpret_cast<const uint64_t*>(p);
+    int64_t nwords = rem >> 3;
+    for (int64_t i = 0; i < nwords; ++i)
+        h += splitmix64(words[i] ^ splitmix64((uint64_t)(ntiles * 128 + i)));
+    int tb = (int)(rem & 7);
+    if (tb) {
+        uint64_t last = 0;
+        const uint8_t* q = p + (nwords << 3);
+        for (int k = 0; k < tb; ++k) last |= ((uint64_t)q[k]) << (8 * k);
+        h += splitmix64(last ^ 0xA5A5A5A5ULL);
+    }
+    h += splitmix64((uint64_t)nbytes ^ 0x1234567890ABCDEFULL);
+    return h;
+}
+
+// wave reduction, one atomic per wave
+__device__ __forceinline__ void lz_mfma_commit(uint64_t h, int lane,
+                                               unsigned long long* out) {
+    for (int off = 32; off > 0; off >>= 1)
+        h += (uint64_t)__shfl_down((long long)h, off, 64);
+    if (lane == 0)
+        atomicAdd(out, (unsigned long long)h);
+}
+
 __global__ void checksum_mfma_kernel(const uint8_t* __restrict__ data,
                                      int64_t nbytes,
                                      unsigned long long* __restrict__ out) {
@@ -752,12 +814,7 @@ __global__ void checksum_mfma_kernel(const uint8_t* __restrict__ data,
     const int wave = threadIdx.x >> 6;
     const int waves_per_block = blockDim.x >> 6;
 
-    // A operand: fixed dense pseudo-random bytes per lane (4 dwords)
-    lz_i32x4 a_frag;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-        a_frag[r] = (int)(uint32_t)(splitmix64(0x5EEDULL * 131 + lane * 4 + r) | 0x01010101u);
-
+    const lz_i32x4 a_frag = lz_mfma_a_frag(lane);
     lz_i32x16 acc = {0};
 
     const int64_t ntiles = nbytes >> 10;  // 1 KiB tiles
@@ -776,52 +833,28 @@ __global__ void checksum_mfma_kernel(const uint8_t* __restrict__ data,
         for (int u = 0; u < U; ++u)
             b[u] = tiles[(t + u * wave_stride) * 64 + lane];
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint64_t s = splitmix64((uint64_t)(t + u * wave_stride));
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                b[u][r] ^= (int)(uint32_t)(s >> ((r * 13) & 31));
-            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_frag, b[u], acc, 0, 0, 0);
-        }
+        for (int u = 0; u < U; ++u)
+            acc = lz_mfma_mix_tile(a_frag, b[u], t + u * wave_stride, acc);
     }
-    for (; t < ntiles; t += wave_stride) {
-        lz_i32x4 b_frag = tiles[t * 64 + lane];
-        const uint64_t s = splitmix64((uint64_t)t);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            b_frag[r] ^= (int)(uint32_t)(s >> ((r * 13) & 31));
-        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_frag, b_frag, acc, 0, 0, 0);
-    }
+    for (; t < ntiles; t += wave_stride)
+        acc = lz_mfma_mix_tile(a_frag, tiles[t * 64 + lane], t, acc);
 
-    // fold accumulators with position salts
-    uint64_t h = 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-        h += splitmix64((uint32_t)acc[r] ^ splitmix64((uint64_t)(lane * 16 + r)));
-
-    // tail (< 1 KiB) + length: one thread via the scalar mix
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const uint8_t* p = data + (ntiles << 10);
-        int64_t rem = nbytes - (ntiles << 10);
-        const uint64_t* words = reinterpret_cast<const uint64_t*>(p);
-        int64_t nwords = rem >> 3;
-        for (int64_t i = 0; i < nwords; ++i)
-            h += splitmix64(words[i] ^ splitmix64((uint64_t)(ntiles * 128 + i)));
-        int tb = (int)(rem & 7);
-        if (tb) {
-            uint64_t last = 0;
-            const uint8_t* q = p + (nwords << 3);
-            for (int k = 0; k < tb; ++k) last |= ((uint64_t)q[k]) << (8 * k);
-            h += splitmix64(last ^ 0xA5A5A5A5ULL);
-        }
-        h += splitmix64((uint64_t)nbytes ^ 0x1234567890ABCDEFULL);
-    }
-
-    for (int off = 32; off > 0; off >>= 1)
-        h += (uint64_t)__shfl_down((long long)h, off, 64);
-    if (lane == 0)
-        atomicAdd(out, (unsigned long long)h);
+    uint64_t h = lz_mfma_fold(acc, lane);
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        h += lz_mfma_tail(data, nbytes);
+    lz_mfma_commit(h, lane, out);
 }
+
+// The grid decides which wave owns which tile, hence the digest: one formula
+// for every kernel that produces it.
+static inline int lz_checksum_mfma_grid(int64_t nbytes) {
+    int64_t tiles = nbytes >> 10;
+    int64_t want = (tiles / 4 + LZ_BLOCK / 64 - 1) / (LZ_BLOCK / 64);
+    return (int)(want < 1 ? 1 : (want > g_max_blocks ? g_max_blocks : want));
+}
+
+extern "C" int lz_get_max_blocks() { return g_max_blocks; }
+extern "C" int lz_checksum_mfma_blocks(int64_t nbytes) { return lz_checksum_mfma_grid(nbytes); }
 
 extern "C" hipError_t lz_checksum_mfma(const void* data, int64_t nbytes,
                                        unsigned long long* out_device,
@@ -829,9 +862,7 @@ extern "C" hipError_t lz_checksum_mfma(const void* data, int64_t nbytes,
     hipStream_t s = (hipStream_t)stream;
     hipError_t err = hipMemsetAsync(out_device, 0, 8, s);
     if (err != hipSuccess) return err;
-    int64_t tiles = nbytes >> 10;
-    int64_t want = (tiles / 4 + LZ_BLOCK / 64 - 1) / (LZ_BLOCK / 64);
-    int blocks = (int)(want < 1 ? 1 : (want > g_max_blocks ? g_max_blocks : want));
+    int blocks = lz_checksum_mfma_grid(nbytes);
     hipLaunchKernelGGL(checksum_mfma_kernel, dim3(blocks), dim3(LZ_BLOCK), 0, s,
                        (const uint8_t*)data, nbytes, out_device);
     return hipGetLastError();
@@ -997,6 +1028,123 @@ __global__ void scale_shift_kernel(const SrcT* __restrict__ src,
     for (int64_t i = tail_start + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
          i < n; i += stride)
         dst[i] = lz_from_float<DstT>(fmaf(lz_to_float<SrcT>(src[i]), a, b));
+}
+
+// scale_shift that also emits what the two usual readers of its output would
+// compute from it: the lz_checksum_mfma digest of dst's bytes and the
+// stats(dst, use_abs) moments, sum|y| and sum y^2 of the stored (rounded)
+// values.  One read of src and one write of dst instead of those plus two
+// more reads of dst.
+//
+// The digest depends on which wave mixes which 1 KiB tile, so the kernel
+// takes the checksum kernel's work decomposition (its grid, wave w owns
+// tiles w, w + wave_stride, ...), not scale_shift_kernel's: a lane's B
+// fragment is the 16 output bytes it has just computed and stored.  Same
+// width on both sides, so the lane's 16 input bytes sit at the same offset.
+// Thread 0 of block 0 computes and stores the sub-1-KiB tail itself and
+// mixes it from dst, as the checksum kernel does.
+//
+// Moments: per lane in f32, one accumulator pair per in-flight tile, folded
+// to f64 per lane and per wave, one f64 atomic per wave (the stats contract).
+// Compiled without packed fp32 ops: dst and the integer-data moments are
+// held bit for bit to the plain kernels.
+template <typename SrcT, typename DstT>
+struct LzEmitTile {
+    static constexpr int E = 16 / (int)sizeof(DstT);
+    struct alignas(16) SrcV { SrcT v[E]; };
+    struct alignas(16) DstV { DstT v[E]; };
+};
+
+template <typename SrcT, typename DstT>
+__device__ __forceinline__ DstT lz_emit_one(SrcT x, float a, float b, float& s,
+                                            float& s2) {
+    DstT o = lz_from_float<DstT>(fmaf(lz_to_float<SrcT>(x), a, b));
+    float y = lz_to_float<DstT>(o);
+    s += fabsf(y);
+    s2 = fmaf(y, y, s2);
+    return o;
+}
+
+template <typename SrcT, typename DstT>
+__device__ __forceinline__ lz_i32x4 lz_emit_tile(
+    const typename LzEmitTile<SrcT, DstT>::SrcV& x,
+    typename LzEmitTile<SrcT, DstT>::DstV* dst, float a, float b, float& s,
+    float& s2) {
+    using Tile = LzEmitTile<SrcT, DstT>;
+    typename Tile::DstV d;
+#pragma unroll
+    for (int k = 0; k < Tile::E; ++k)
+        d.v[k] = lz_emit_one<SrcT, DstT>(x.v[k], a, b, s, s2);
+    *dst = d;
+    lz_i32x4 bytes;
+    __builtin_memcpy(&bytes, &d, 16);
+    return bytes;
+}
+
+template <typename SrcT, typename DstT>
+__global__ void __launch_bounds__(LZ_BLOCK) LZ_NO_PK_F32
+scale_shift_emit_kernel(const SrcT* src, DstT* dst, int64_t n, float a, float b,
+                        unsigned long long* __restrict__ digest,
+                        double* __restrict__ moments) {
+    static_assert(sizeof(SrcT) == sizeof(DstT), "same-width pairs only");
+    using Tile = LzEmitTile<SrcT, DstT>;
+    using SrcV = typename Tile::SrcV;
+    using DstV = typename Tile::DstV;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int waves_per_block = blockDim.x >> 6;
+
+    const lz_i32x4 a_frag = lz_mfma_a_frag(lane);
+    lz_i32x16 acc = {0};
+
+    const int64_t nbytes = n * (int64_t)sizeof(DstT);
+    const int64_t ntiles = nbytes >> 10;
+    const int64_t wave_id = (int64_t)blockIdx.x * waves_per_block + wave;
+    const int64_t wave_stride = (int64_t)gridDim.x * waves_per_block;
+    const SrcV* srcv = reinterpret_cast<const SrcV*>(src);
+    DstV* dstv = reinterpret_cast<DstV*>(dst);
+
+    constexpr int U = 4;
+    float s[U] = {0.f}, s2[U] = {0.f};
+    int64_t t = wave_id;
+    for (; t + (U - 1) * wave_stride < ntiles; t += (int64_t)U * wave_stride) {
+        SrcV x[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            x[u] = srcv[(t + u * wave_stride) * 64 + lane];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t tu = t + u * wave_stride;
+            lz_i32x4 bytes = lz_emit_tile<SrcT, DstT>(x[u], &dstv[tu * 64 + lane],
+                                                      a, b, s[u], s2[u]);
+            acc = lz_mfma_mix_tile(a_frag, bytes, tu, acc);
+        }
+    }
+    for (; t < ntiles; t += wave_stride) {
+        SrcV x = srcv[t * 64 + lane];
+        lz_i32x4 bytes = lz_emit_tile<SrcT, DstT>(x, &dstv[t * 64 + lane], a, b,
+                                                  s[0], s2[0]);
+        acc = lz_mfma_mix_tile(a_frag, bytes, t, acc);
+    }
+
+    uint64_t h = lz_mfma_fold(acc, lane);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (int64_t i = (ntiles << 10) / (int64_t)sizeof(DstT); i < n; ++i)
+            dst[i] = lz_emit_one<SrcT, DstT>(src[i], a, b, s[0], s2[0]);
+        // reads back this thread's own stores: ordered within the thread
+        h += lz_mfma_tail(reinterpret_cast<const uint8_t*>(dst), nbytes);
+    }
+    lz_mfma_commit(h, lane, digest);
+
+    double ds = 0, ds2 = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) { ds += (double)s[u]; ds2 += (double)s2[u]; }
+    ds = lz_wave_reduce_f64(ds);
+    ds2 = lz_wave_reduce_f64(ds2);
+    if (lane == 0) {
+        atomicAdd(&moments[0], ds);
+        atomicAdd(&moments[1], ds2);
+    }
 }
 
 // dst = cast(alpha*a + beta*b) — fused binary combine (tree-merge stages)
@@ -1188,6 +1336,47 @@ extern "C" hipError_t lz_scale_shift(const void* src, int src_dtype, void* dst,
     }
 #undef LZ_SS_SRC
 #undef LZ_SS_DST
+    return hipGetLastError();
+}
+
+// scale_shift + digest + moments in one pass (scale_shift_emit_kernel).
+// Same-width float pairs only, src and dst 16-byte aligned; anything else is
+// hipErrorInvalidValue and the caller runs lz_scale_shift.  The outputs are
+// one 24-byte buffer, zeroed here by one memset: digest_out points at its
+// first 8 bytes, moments_out at the 16 that follow.  The grid is
+// lz_checksum_mfma's on dst's bytes (lz_checksum_mfma_blocks), so the digest
+// is the one lz_checksum_mfma(dst) would write under the same block cap.
+extern "C" hipError_t lz_scale_shift_emit(const void* src, int src_dtype, void* dst,
+                                          int dst_dtype, int64_t n, float a, float b,
+                                          unsigned long long* digest_out,
+                                          double* moments_out, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (n < 0 || (((uintptr_t)src | (uintptr_t)dst) & 15) != 0 ||
+        ((uintptr_t)digest_out & 7) != 0 ||
+        (void*)moments_out != (void*)(digest_out + 1))
+        return hipErrorInvalidValue;
+    const bool both16 = (src_dtype == LZ_F16 || src_dtype == LZ_BF16) &&
+                        (dst_dtype == LZ_F16 || dst_dtype == LZ_BF16);
+    if (!both16 && !(src_dtype == LZ_F32 && dst_dtype == LZ_F32))
+        return hipErrorInvalidValue;
+    hipError_t err = hipMemsetAsync(digest_out, 0, 24, s);
+    if (err != hipSuccess) return err;
+    int blocks = lz_checksum_mfma_grid(n * (dst_dtype == LZ_F32 ? 4 : 2));
+#define LZ_SSE_LAUNCH(SrcT, DstT)                                               \
+    hipLaunchKernelGGL((scale_shift_emit_kernel<SrcT, DstT>), dim3(blocks),     \
+                       dim3(LZ_BLOCK), 0, s, (const SrcT*)src, (DstT*)dst, n,   \
+                       a, b, digest_out, moments_out)
+    if (!both16)
+        LZ_SSE_LAUNCH(float, float);
+    else if (src_dtype == LZ_F16 && dst_dtype == LZ_F16)
+        LZ_SSE_LAUNCH(__half, __half);
+    else if (src_dtype == LZ_F16)
+        LZ_SSE_LAUNCH(__half, __hip_bfloat16);
+    else if (dst_dtype == LZ_F16)
+        LZ_SSE_LAUNCH(__hip_bfloat16, __half);
+    else
+        LZ_SSE_LAUNCH(__hip_bfloat16, __hip_bfloat16);
+#undef LZ_SSE_LAUNCH
     return hipGetLastError();
 }
 
