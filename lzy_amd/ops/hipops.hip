@@ -80,6 +80,20 @@ template <> __device__ __forceinline__ int32_t lz_from_float<int32_t>(float v) {
 template <> __device__ __forceinline__ int64_t lz_from_float<int64_t>(float v) { return (int64_t)v; }
 template <> __device__ __forceinline__ double lz_from_float<double>(float v) { return (double)v; }
 
+// The last step of every combine kernel (scale_shift, normalize, axpby and the
+// decode-combines): r is the fp32 result of the FMA, rounded to fp32 already,
+// and is rounded again to DstT.  Left to itself the compiler fuses an FMA and
+// an f16 convert into one v_fma_mixlo_f16 wherever the code's shape allows,
+// which rounds the exact sum once; the empty asm makes r a value of its own,
+// so every path of every kernel rounds twice (docs/mxwire.md).
+template <typename DstT>
+__device__ __forceinline__ DstT lz_narrow(float r) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (std::is_same<DstT, __half>::value) asm("" : "+v"(r));
+#endif
+    return lz_from_float<DstT>(r);
+}
+
 // One element of cast_copy.  Pairs of plain arithmetic types (f32, f64, i32,
 // i64, u8) convert directly, so i32/i64/f64 keep every bit the destination
 // can hold; any pair with a 16- or 8-bit float goes through f32, the only
@@ -994,13 +1008,13 @@ __global__ void normalize_apply_kernel(const SrcT* __restrict__ src,
         DstV d;
 #pragma unroll
         for (int k = 0; k < V; ++k)
-            d.v[k] = lz_from_float<DstT>((lz_to_float<SrcT>(x.v[k]) - mean) * rstd);
+            d.v[k] = lz_narrow<DstT>((lz_to_float<SrcT>(x.v[k]) - mean) * rstd);
         dstv[i] = d;
     }
     int64_t tail_start = vec_n * V;
     for (int64_t i = tail_start + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
          i < n; i += stride)
-        dst[i] = lz_from_float<DstT>((lz_to_float<SrcT>(src[i]) - mean) * rstd);
+        dst[i] = lz_narrow<DstT>((lz_to_float<SrcT>(src[i]) - mean) * rstd);
 }
 
 // dst = cast(src * a + b) — fused affine (one FMA per element)
@@ -1021,13 +1035,13 @@ __global__ void scale_shift_kernel(const SrcT* __restrict__ src,
         DstV d;
 #pragma unroll
         for (int k = 0; k < V; ++k)
-            d.v[k] = lz_from_float<DstT>(fmaf(lz_to_float<SrcT>(x.v[k]), a, b));
+            d.v[k] = lz_narrow<DstT>(fmaf(lz_to_float<SrcT>(x.v[k]), a, b));
         dstv[i] = d;
     }
     int64_t tail_start = vec_n * V;
     for (int64_t i = tail_start + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
          i < n; i += stride)
-        dst[i] = lz_from_float<DstT>(fmaf(lz_to_float<SrcT>(src[i]), a, b));
+        dst[i] = lz_narrow<DstT>(fmaf(lz_to_float<SrcT>(src[i]), a, b));
 }
 
 // scale_shift that also emits what the two usual readers of its output would
@@ -1058,7 +1072,7 @@ struct LzEmitTile {
 template <typename SrcT, typename DstT>
 __device__ __forceinline__ DstT lz_emit_one(SrcT x, float a, float b, float& s,
                                             float& s2) {
-    DstT o = lz_from_float<DstT>(fmaf(lz_to_float<SrcT>(x), a, b));
+    DstT o = lz_narrow<DstT>(fmaf(lz_to_float<SrcT>(x), a, b));
     float y = lz_to_float<DstT>(o);
     s += fabsf(y);
     s2 = fmaf(y, y, s2);
@@ -1167,7 +1181,7 @@ __global__ void axpby_kernel(const SrcT* __restrict__ a,
         DstV d;
 #pragma unroll
         for (int k = 0; k < V; ++k)
-            d.v[k] = lz_from_float<DstT>(
+            d.v[k] = lz_narrow<DstT>(
                 fmaf(lz_to_float<SrcT>(x.v[k]), alpha,
                      lz_to_float<SrcT>(y.v[k]) * beta));
         dstv[i] = d;
@@ -1175,7 +1189,7 @@ __global__ void axpby_kernel(const SrcT* __restrict__ a,
     int64_t tail_start = vec_n * V;
     for (int64_t i = tail_start + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
          i < n; i += stride)
-        dst[i] = lz_from_float<DstT>(
+        dst[i] = lz_narrow<DstT>(
             fmaf(lz_to_float<SrcT>(a[i]), alpha, lz_to_float<SrcT>(b[i]) * beta));
 }
 
@@ -1470,7 +1484,7 @@ __device__ __forceinline__ void lz_mx8_axpby_store(const float (&fa)[8], uint32_
     DstT y[V];
 #pragma unroll
     for (int k = 0; k < V; ++k)
-        y[k] = lz_from_float<DstT>(fmaf(fa[k], alpha, x[k] * beta));
+        y[k] = lz_narrow<DstT>(fmaf(fa[k], alpha, x[k] * beta));
     if (FULL) {
         LzVec16 q[sizeof(DstT) * V / 16];
         __builtin_memcpy(q, y, sizeof(y));
@@ -1794,17 +1808,10 @@ __device__ __forceinline__ void lz_mx4_dec_store(uint32_t w, uint32_t b,
     DstT y[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-        float r = x[k];
-        if constexpr (COMBINE) {
-            r = fmaf(fa[k], alpha, x[k] * beta);
-            // the contract rounds to fp32, then to the 16-bit type: keep the
-            // FMA and the f16 convert from fusing into one single-rounding
-            // v_fma_mixlo_f16
-#if defined(__HIP_DEVICE_COMPILE__)
-            if constexpr (std::is_same<DstT, __half>::value) asm("" : "+v"(r));
-#endif
-        }
-        y[k] = lz_from_float<DstT>(r);
+        if constexpr (COMBINE)
+            y[k] = lz_narrow<DstT>(fmaf(fa[k], alpha, x[k] * beta));
+        else
+            y[k] = lz_from_float<DstT>(x[k]);
     }
     if (FULL) {
         LzVec16 q[sizeof(DstT) * V / 16];
@@ -2036,13 +2043,7 @@ __device__ __forceinline__ void lz_mx4f_fetch(const void* src2,
 // combine one group, store it to dst and leave in r what the encoder sees:
 // the stored value as fp32, +0.0 at positions >= n.  FULL: all 8 elements
 // lie inside [0, n) and dst + e0 is 16 B-aligned.
-//
-// TWO_STEP (f16 dst only): the fp32 FMA result is a value of its own (the
-// empty asm), so the f16 convert rounds a second time and cannot fuse with
-// the FMA into one single-rounding v_fma_mixlo_f16.  mx4_decode_kernel does
-// so on every path; axpby_kernel on every whole group, while the elements of
-// a group cut by n take its fused tail loop.
-template <typename DstT, bool WIRE, bool FULL, bool TWO_STEP>
+template <typename DstT, bool WIRE, bool FULL>
 __device__ __forceinline__ void lz_mx4f_combine(const float (&fa)[8],
                                                 const LzMx4Second& s, DstT* dst,
                                                 int64_t e0, int64_t n, float alpha,
@@ -2066,12 +2067,7 @@ __device__ __forceinline__ void lz_mx4f_combine(const float (&fa)[8],
     DstT y[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-        float t = fmaf(fa[k], alpha, x[k] * beta);
-#if defined(__HIP_DEVICE_COMPILE__)
-        if constexpr (TWO_STEP && std::is_same<DstT, __half>::value)
-            asm volatile("" : "+v"(t));
-#endif
-        y[k] = lz_from_float<DstT>(t);
+        y[k] = lz_narrow<DstT>(fmaf(fa[k], alpha, x[k] * beta));
         r[k] = (FULL || e0 + k < n) ? lz_to_float<DstT>(y[k]) : 0.f;
     }
     if (FULL) {
@@ -2104,14 +2100,11 @@ __device__ __forceinline__ void lz_mx4f_one(const SrcT* a, const void* src2,
     if (ALIGNED && e0 + 8 <= n) {
         lz_mx4f_fetch<SrcT, WIRE, ALIGNED, true>(src2, scales_in, g, n, s);
         lz_mx8_load<SrcT, true>(a, e0, n, fa);
-        lz_mx4f_combine<DstT, WIRE, true, true>(fa, s, dst, e0, n, alpha, beta, r);
+        lz_mx4f_combine<DstT, WIRE, true>(fa, s, dst, e0, n, alpha, beta, r);
     } else {
         lz_mx4f_fetch<SrcT, WIRE, ALIGNED, false>(src2, scales_in, g, n, s);
         lz_mx8_load<SrcT, false>(a, e0, n, fa);
-        if (WIRE || e0 + 8 <= n)
-            lz_mx4f_combine<DstT, WIRE, false, true>(fa, s, dst, e0, n, alpha, beta, r);
-        else
-            lz_mx4f_combine<DstT, WIRE, false, false>(fa, s, dst, e0, n, alpha, beta, r);
+        lz_mx4f_combine<DstT, WIRE, false>(fa, s, dst, e0, n, alpha, beta, r);
     }
 }
 
@@ -2143,10 +2136,8 @@ mx4_axpby_pack_kernel(const SrcT* a, const void* src2, DstT* dst,
             // left alone the scheduler sinks the second group's load of a
             // behind the first group's wait, to reuse its registers
             __builtin_amdgcn_sched_barrier(0);
-            lz_mx4f_combine<DstT, WIRE, true, true>(fa, sa, dst, ga * 8, n, alpha, beta,
-                                                    ra);
-            lz_mx4f_combine<DstT, WIRE, true, true>(fb, sb, dst, gb * 8, n, alpha, beta,
-                                                    rb);
+            lz_mx4f_combine<DstT, WIRE, true>(fa, sa, dst, ga * 8, n, alpha, beta, ra);
+            lz_mx4f_combine<DstT, WIRE, true>(fb, sb, dst, gb * 8, n, alpha, beta, rb);
             lz_mx4_emit<true, true>(ra, ga, lane, ngroups, nblk, wire_out, scales_out);
             lz_mx4_emit<true, true>(rb, gb, lane, ngroups, nblk, wire_out, scales_out);
         } else {
@@ -2435,16 +2426,10 @@ __device__ __forceinline__ void lz_mx6_dec_store(const LzVec12& pv, uint32_t b,
     for (int k = 0; k < V; ++k) {
         float r = __builtin_ldexpf(x[k], e);
         r = b == 0xffu ? __uint_as_float(0x7fc00000u) : r;
-        if constexpr (COMBINE) {
-            r = fmaf(fa[k], alpha, r * beta);
-            // the contract rounds to fp32, then to the 16-bit type: keep the
-            // FMA and the f16 convert from fusing into one single-rounding
-            // v_fma_mixlo_f16
-#if defined(__HIP_DEVICE_COMPILE__)
-            if constexpr (std::is_same<DstT, __half>::value) asm("" : "+v"(r));
-#endif
-        }
-        y[k] = lz_from_float<DstT>(r);
+        if constexpr (COMBINE)
+            y[k] = lz_narrow<DstT>(fmaf(fa[k], alpha, r * beta));
+        else
+            y[k] = lz_from_float<DstT>(r);
     }
     if (FULL) {
         LzVec16 q[sizeof(DstT) * V / 16];
@@ -2658,15 +2643,7 @@ __device__ __forceinline__ void lz_mxf_fetch(const void* src2,
 // combine one group, store it to dst and leave in r what the encoder sees:
 // the stored value as fp32, +0.0 at positions >= n.  FULL: all 8 elements
 // lie inside [0, n) and dst + e0 is 16 B-aligned.
-//
-// TWO_STEP (f16 dst only): the combine kernels reach an f16 two ways.  Where
-// they store a whole group, the fp32 FMA result is converted (two roundings);
-// elsewhere the compiler fuses FMA and convert into v_fma_mixlo_f16, which
-// rounds the exact sum once.  The two differ on about one element in 2^14.
-// dst must be the combine kernels' bit for bit, so this kernel takes, group
-// by group, the way they take (lz_mxf_two_step below); the empty asm keeps
-// the fp32 result a value of its own, which rules the fused form out.
-template <typename DstT, bool WIRE, bool FULL, bool TWO_STEP, int CODEC>
+template <typename DstT, bool WIRE, bool FULL, int CODEC>
 __device__ __forceinline__ void lz_mxf_combine(const float (&fa)[8], const LzMxSecond& s,
                                                DstT* dst, int64_t e0, int64_t n,
                                                float alpha, float beta, float (&r)[8]) {
@@ -2685,10 +2662,7 @@ __device__ __forceinline__ void lz_mxf_combine(const float (&fa)[8], const LzMxS
     DstT y[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-        float t = fmaf(fa[k], alpha, x[k] * beta);
-        if constexpr (TWO_STEP && std::is_same<DstT, __half>::value)
-            asm volatile("" : "+v"(t));
-        y[k] = lz_from_float<DstT>(t);
+        y[k] = lz_narrow<DstT>(fmaf(fa[k], alpha, x[k] * beta));
         r[k] = (FULL || e0 + k < n) ? lz_to_float<DstT>(y[k]) : 0.f;
     }
     if (FULL) {
@@ -2702,16 +2676,6 @@ __device__ __forceinline__ void lz_mxf_combine(const float (&fa)[8], const LzMxS
         for (int k = 0; k < V; ++k)
             if (e0 + k < n) dst[e0 + k] = y[k];
     }
-}
-
-// how the kernel this one stands in for rounds a whole group (all 8 elements
-// inside [0, n)) to f16.  lz_mx_axpby_body: two steps on its 16 B-store path
-// of the MXFP8 kernels, fused everywhere in the MXINT8 ones (compiled without
-// packed fp32 ops).  axpby_kernel: two steps on every whole group, aligned
-// or not.  A group cut by n is fused in all of them.
-template <bool WIRE, bool FULL, int CODEC>
-constexpr bool lz_mxf_two_step() {
-    return WIRE ? (FULL && CODEC == LZ_MXFP8) : true;
 }
 
 // one group on the guarded path (the tail, and element-aligned views).  The
@@ -2731,17 +2695,11 @@ __device__ __forceinline__ void lz_mxf_one(const SrcT* a, const void* src2,
     if (ALIGNED && e0 + 8 <= n) {
         lz_mxf_fetch<SrcT, WIRE, ALIGNED, true>(src2, scales_in, g, n, s);
         lz_mx8_load<SrcT, true>(a, e0, n, fa);
-        lz_mxf_combine<DstT, WIRE, true, lz_mxf_two_step<WIRE, true, CODEC>(), CODEC>(
-            fa, s, dst, e0, n, alpha, beta, r);
+        lz_mxf_combine<DstT, WIRE, true, CODEC>(fa, s, dst, e0, n, alpha, beta, r);
     } else {
         lz_mxf_fetch<SrcT, WIRE, ALIGNED, false>(src2, scales_in, g, n, s);
         lz_mx8_load<SrcT, false>(a, e0, n, fa);
-        if (!ALIGNED && e0 + 8 <= n && lz_mxf_two_step<WIRE, false, CODEC>())
-            lz_mxf_combine<DstT, WIRE, false, true, CODEC>(fa, s, dst, e0, n, alpha, beta,
-                                                           r);
-        else
-            lz_mxf_combine<DstT, WIRE, false, false, CODEC>(fa, s, dst, e0, n, alpha,
-                                                            beta, r);
+        lz_mxf_combine<DstT, WIRE, false, CODEC>(fa, s, dst, e0, n, alpha, beta, r);
     }
 }
 
@@ -2770,11 +2728,8 @@ mx_axpby_pack_kernel(const SrcT* a, const void* src2, DstT* dst,
             lz_mxf_fetch<SrcT, WIRE, true, true>(src2, scales_in, gb, n, sb);
             lz_mx8_load<SrcT, true>(a, ga * 8, n, fa);
             lz_mx8_load<SrcT, true>(a, gb * 8, n, fb);
-            constexpr bool TS = lz_mxf_two_step<WIRE, true, CODEC>();
-            lz_mxf_combine<DstT, WIRE, true, TS, CODEC>(fa, sa, dst, ga * 8, n, alpha, beta,
-                                                        ra);
-            lz_mxf_combine<DstT, WIRE, true, TS, CODEC>(fb, sb, dst, gb * 8, n, alpha, beta,
-                                                        rb);
+            lz_mxf_combine<DstT, WIRE, true, CODEC>(fa, sa, dst, ga * 8, n, alpha, beta, ra);
+            lz_mxf_combine<DstT, WIRE, true, CODEC>(fb, sb, dst, gb * 8, n, alpha, beta, rb);
             lz_mx8_emit<true, true, CODEC>(ra, ga, lane, ngroups, nblk, wire_out,
                                            scales_out);
             lz_mx8_emit<true, true, CODEC>(rb, gb, lane, ngroups, nblk, wire_out,

@@ -595,3 +595,266 @@ def assert_bits_equal(got: torch.Tensor, bits: np.ndarray, nan: np.ndarray,
             f"{what}: {int(bad.sum())} of {bad.size} elements differ; first at "
             f"{idx.tolist()}: got {[hex(v) for v in gb[idx].tolist()]} "
             f"want {[hex(v) for v in bits[idx].tolist()]}")
+
+
+# ---------------------------------------------------------------------------
+# the combine contract: dst = round_dst(round_f32(a*alpha + fl32(x*beta)))
+#
+# axpby, scale_shift (x*a + b is the same with p = b) and every
+# decode-combine promise it (docs/mxwire.md).  fma_ref takes the sum exactly;
+# the sets below are built so that a kernel which rounds the exact sum once,
+# or sums in another order, gives other bits.
+# ---------------------------------------------------------------------------
+
+F32, F16, BF16 = torch.float32, torch.float16, torch.bfloat16
+FLOATS3 = (F32, BF16, F16)
+DT_NAMES = {F32: "f32", BF16: "bf16", F16: "f16"}
+
+
+def _as_f64(v) -> np.ndarray:
+    """Values of an f32/bf16/f16 tensor, or of an array that already holds
+    fp32-representable values, as float64 (exact)."""
+    if isinstance(v, torch.Tensor):
+        return v.detach().reshape(-1).to(torch.float64).numpy()
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        back = v.astype(np.float32).astype(np.float64)
+    assert ((back == v) | np.isnan(v)).all(), "operands must be fp32 values"
+    return v
+
+
+def _round_to_odd_f32(v: np.ndarray) -> np.ndarray:
+    """float64 -> fp32, rounding to odd: exact values stay, any other goes
+    to the neighbour whose last mantissa bit is set.  A later RNE to a format
+    of at most 22 bits then rounds the float64 value once."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = v.astype(np.float32)
+        back = f.astype(np.float64)
+        inexact = np.isfinite(v) & (back != v)
+        # RNE may have carried a huge finite value to Inf: come back to max
+        f = np.where(inexact & np.isinf(f), np.copysign(np.finfo(np.float32).max, f), f)
+        back = f.astype(np.float64)
+        even = (f.view(np.uint32) & np.uint32(1)) == 0
+        toward = np.where(v > back, np.float32(np.inf), np.float32(-np.inf))
+        return np.where(inexact & even, np.nextafter(f, toward), f).astype(np.float32)
+
+
+def _narrow_f32(f: np.ndarray, dst_dtype) -> np.ndarray:
+    """fp32 -> bit patterns of dst_dtype, one RNE (NaN bits unspecified)."""
+    f = np.ascontiguousarray(f, dtype=np.float32)
+    if dst_dtype == F32:
+        return f.view(np.uint32).copy()
+    with np.errstate(over="ignore", invalid="ignore"):
+        if dst_dtype == F16:
+            return f.astype(np.float16).view(np.uint16)
+    assert dst_dtype == BF16
+    b = f.view(np.uint32).astype(np.uint64)
+    b = b + np.uint64(0x7FFF) + ((b >> np.uint64(16)) & np.uint64(1))
+    return (b >> np.uint64(16)).astype(np.uint16)
+
+
+def fma_ref(a, alpha, x, beta, dst_dtype, two_step=True):
+    """The combine contract, exactly rounded.  p = fl32(x*beta): the float64
+    product of two fp32 values is exact and one cast rounds it.  v = a*alpha
+    + p is taken exactly: a*alpha is exact in float64, TwoSum gives the
+    float64 sum s and its error e, and s is moved to its odd neighbour when
+    e != 0 (round to odd; 53 >= 2*24 + 2, so the fp32 rounding that follows
+    is the rounding of v itself).  Then fp32 -> dst_dtype.  two_step=False
+    rounds v straight to dst_dtype instead (used to build and check inputs).
+    Returns (bit patterns, NaN mask); bits at NaN positions are unspecified.
+    Inf, NaN, overflow, subnormals and signed zeros follow IEEE 754."""
+    a64, x64 = _as_f64(a), _as_f64(x)
+    al, be = np.float64(np.float32(alpha)), np.float64(np.float32(beta))
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        p = (x64 * be).astype(np.float32).astype(np.float64)
+        t = a64 * al                                   # <= 48 bits: exact
+        s = t + p
+        bb = s - t
+        e = (t - (s - bb)) + (p - bb)                  # TwoSum: t + p == s + e
+        e = np.where(np.isfinite(s), e, 0.0)
+        even = (s.view(np.uint64) & np.uint64(1)) == 0
+        # e > 0 moves up the real line, whatever the sign of s
+        odd = np.where((e != 0) & even, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+        nan = np.isnan(odd)
+        if two_step or dst_dtype == F32:
+            bits = _narrow_f32(odd.astype(np.float32), dst_dtype)
+        elif dst_dtype == F16:
+            bits = odd.astype(np.float16).view(np.uint16)   # numpy: one rounding
+        else:
+            bits = _narrow_f32(_round_to_odd_f32(odd), dst_dtype)
+    return bits.astype(_MX_BITS[dst_dtype]), nan
+
+
+# --- wire codecs as (pack, decode) of fp32 values, from the CPU references ---
+
+MX_CODECS = ("mx8", "mxi8", "mx4", "mx6")
+
+
+def mx_pack_ref(codec: str, x) -> torch.Tensor:
+    """Reference wire buffer (uint8 tensor) of an f32/bf16/f16 tensor."""
+    x = x.detach().reshape(-1).to(F32)
+    if codec == "mx8":
+        return mx8_wire_ref(x)
+    import test_mxfp4, test_mxfp6, test_mxint8
+    pack = {"mxi8": test_mxint8.mxi8_pack_ref, "mx4": test_mxfp4.mx4_pack_ref,
+            "mx6": test_mxfp6.mx6_pack_ref}[codec]
+    return torch.from_numpy(np.ascontiguousarray(pack(x.numpy()), dtype=np.uint8))
+
+
+def mx_decode_ref(codec: str, wire, n: int) -> np.ndarray:
+    """Reference decode of a wire buffer: float64, exact, NaN where the
+    format says NaN."""
+    w = np.ascontiguousarray(wire.numpy() if isinstance(wire, torch.Tensor) else wire)
+    if codec == "mx8":
+        nblk = (n + MX_BLOCK - 1) // MX_BLOCK
+        bits, nan = mx8_unpack_ref(w[: 32 * nblk], w[32 * nblk:], n, F32)
+        return np.where(nan, np.nan, from_bits(bits, F32).double().numpy())
+    import test_mxfp4, test_mxfp6, test_mxint8
+    dec = {"mxi8": test_mxint8.mxi8_unpack_ref, "mx4": test_mxfp4.mx4_unpack_ref,
+           "mx6": test_mxfp6.mx6_unpack_ref}[codec]
+    return np.asarray(dec(w, n), dtype=np.float64)
+
+
+# --- input sets ---------------------------------------------------------------
+
+COMBINE_N = 4128          # 129 blocks: every shape of the GPU tests is a prefix
+# significant bits of a midpoint between neighbours of the 16-bit formats
+_MID_BITS = {F16: 12, BF16: 9}
+
+
+def _f32_exact(v: np.ndarray) -> np.ndarray:
+    assert (v.astype(np.float32).astype(np.float64) == v).all()
+    return v
+
+
+def _all_dtypes_exact(v: np.ndarray) -> None:
+    t = torch.from_numpy(v)
+    for d in FLOATS3:
+        assert torch.equal(t.to(d).double(), t), f"not exact in {d}"
+
+
+def dr_axpby_set(mid_dtype):
+    """(a, alpha, x, beta), float64 arrays of COMBINE_N values exact in f32,
+    bf16 and f16, whose exact sum a*alpha + x*beta lies just off a midpoint
+    m between neighbours of ``mid_dtype``, by 0 < |d| < ulp32(m)/2: fl32 of
+    the sum is m, a tie, so rounding in two steps goes to the even neighbour
+    and rounding the exact sum once goes wherever d points.
+
+    a = +-(1 + j/128) * 2^k (j < 126: the sum stays in a's binade), alpha = 1, x = +-{1, 3} * 2^k with k in [-6, 6]
+    constant over a 32-element block (so every wire codec holds x exactly),
+    beta = 2^-h * (1 + 2^-g): x*beta supplies the half ulp of mid_dtype
+    (h = 11 for f16, 8 for bf16) and the d below fp32's reach."""
+    h, g = {F16: (11, 16), BF16: (8, 19)}[mid_dtype]
+    rng = np.random.default_rng(20 + h)
+    i = np.arange(COMBINE_N)
+    k = ((i // MX_BLOCK) % 13 - 6).astype(np.int64)
+    a = np.ldexp((1 + (i % 126) / 128) * rng.choice([-1.0, 1.0], COMBINE_N), k)
+    x = np.ldexp(rng.choice([1.0, 3.0], COMBINE_N) * rng.choice([-1.0, 1.0], COMBINE_N), k)
+    beta = 2.0 ** -h * (1 + 2.0 ** -g)
+    assert float(np.float32(beta)) == beta
+    _all_dtypes_exact(a), _all_dtypes_exact(x)
+    _f32_exact(x * beta)                               # the product is not rounded
+    # the fp32 sum is the midpoint: a + x * 2^-h, at most _MID_BITS bits
+    m = a + x * 2.0 ** -h
+    d = x * beta - x * 2.0 ** -h
+    ulp32 = np.ldexp(1.0, np.frexp(m)[1] - 24)
+    assert (m != 0).all() and (np.abs(d) > 0).all() and (np.abs(d) < ulp32 / 2).all()
+    assert (np.ldexp(m, _MID_BITS[mid_dtype] - np.frexp(m)[1]) % 1 == 0).all()
+    return a, 1.0, x, beta
+
+
+def dr_scale_shift_sets(mid_dtype, src_dtype):
+    """[(x, a, b)] for dst = x*a + b: the scalar b is the part below fp32's
+    reach and x*a is the midpoint, |x*a| in [2^-4, 2^6) so that |b| = 2^-40
+    < ulp32/2.  An f32 source carries the midpoint itself (a = 1); a 16-bit
+    source is +-2^k and a scalar ``a`` carries the midpoint's mantissa, a
+    few of them.  Both signs of b."""
+    nb = _MID_BITS[mid_dtype]
+    rng = np.random.default_rng(30 + nb)
+    i = np.arange(COMBINE_N)
+    k = (i % 10 - 4).astype(np.int64)
+    sign = rng.choice([-1.0, 1.0], COMBINE_N)
+    out = []
+    if src_dtype == F32:
+        odd = 2 * rng.integers(2 ** (nb - 2), 2 ** (nb - 1), COMBINE_N) + 1   # nb bits, odd
+        x = _f32_exact(np.ldexp(odd * sign, k - (nb - 1)))
+        out = [(x, 1.0, b) for b in (2.0 ** -40, -(2.0 ** -40))]
+    else:
+        x = np.ldexp(sign, k)
+        _all_dtypes_exact(x)
+        top = 2 ** (nb - 1)
+        for j, b in ((1, 2.0 ** -40), (top - 1, -(2.0 ** -40)), (top // 2 + 3, 2.0 ** -40),
+                     (top // 2 - 2, -(2.0 ** -40)), (5, -(2.0 ** -40)), (top - 4, 2.0 ** -40)):
+            a = (top + 2 * (j // 2) + 1) / top         # 1.f, nb bits, the last one set
+            out.append((x, a, b))
+    for x, a, b in out:
+        assert float(np.float32(a)) == a and float(np.float32(b)) == b
+        m = _f32_exact(x * a)                          # the midpoint, exact
+        assert ((np.abs(m) >= 2.0 ** -4) & (np.abs(m) < 2.0 ** 6)).all()
+        assert (np.ldexp(m, nb - np.frexp(m)[1]) % 2 == 1).all()      # nb bits, odd
+        assert abs(b) < np.ldexp(1.0, np.frexp(m)[1] - 24).min() / 2
+    return out
+
+
+def dr_disagreement(a, alpha, x, beta, dst_dtype) -> float:
+    """Share of elements on which rounding in two steps and rounding the
+    exact sum once give different bits."""
+    two, _ = fma_ref(a, alpha, x, beta, dst_dtype, two_step=True)
+    one, _ = fma_ref(a, alpha, x, beta, dst_dtype, two_step=False)
+    return float((two != one).mean())
+
+
+INEXACT_SCALARS = ((0.3, -1.7), (1 / 3, 2 / 3))
+
+
+@functools.lru_cache(maxsize=None)
+def inexact_set(src_dtype):
+    """(a, x) tensors of ``src_dtype``: randn times {1e-4, 1, 3e3}, the
+    factor changing from block to block.  With INEXACT_SCALARS the product
+    x*beta is rounded and the sum is a generic real number."""
+    g = torch.Generator().manual_seed(77)
+    f = torch.tensor([1e-4, 1.0, 3e3]).repeat_interleave(MX_BLOCK).repeat(COMBINE_N // 96 + 1)
+    a = (torch.randn(COMBINE_N, generator=g) * f[:COMBINE_N]).to(src_dtype)
+    x = (torch.randn(COMBINE_N, generator=g) * f.roll(MX_BLOCK)[:COMBINE_N]).to(src_dtype)
+    return a, x
+
+
+def _tiny(dtype) -> float:
+    return {F32: 2.0 ** -149, F16: 2.0 ** -24, BF16: 2.0 ** -133}[dtype]
+
+
+@functools.lru_cache(maxsize=None)
+def specials_runs(src_dtype):
+    """[(name, a, x, alpha, beta)] with a, x tensors of ``src_dtype``:
+    - "cross": every pair of +-Inf, NaN, +-0, +-the smallest subnormal, +-1
+      and +-max under (1, 1) -- Inf - Inf, fma(0, 1, -0.0), fp32 overflow of
+      the sum of two maxima (bf16, f32) -- and under beta = Inf (0 * Inf);
+    - "f16sub"/"bf16sub": small integers times 2^-24, 2^-25 (2^-133, 2^-134):
+      results among the f16 (bf16) subnormals and on their ties, the fp32
+      sum itself subnormal in the second;
+    - "edge": 65504 + {0, 8, 16, ...}: 65520 is the tie that rounds an f16
+      to Inf, 65519.99 (beta 7.995) stays 65504;
+    - "ovf": max * 2^112 twice: the fp32 sum overflows for every source."""
+    inf, nan = float("inf"), float("nan")
+    big = float(torch.finfo(src_dtype).max)
+    v = [inf, -inf, nan, 0.0, -0.0, _tiny(src_dtype), -_tiny(src_dtype), 1.0, -1.0, big, -big]
+    va = torch.tensor(v, dtype=torch.float64).repeat_interleave(len(v)).to(src_dtype)
+    vx = torch.tensor(v, dtype=torch.float64).repeat(len(v)).to(src_dtype)
+    ints = torch.arange(-40, 41, dtype=torch.float64)
+    ia = ints.repeat_interleave(9).to(src_dtype)
+    ix = torch.tensor([-3.0, -2, -1, -0.0, 0, 1, 2, 3, 5], dtype=torch.float64).repeat(81).to(src_dtype)
+    ea = torch.tensor([1.0, -1.0], dtype=torch.float64).repeat_interleave(9).to(src_dtype)
+    ex = torch.tensor([0.0, 1, 2, 3, 4, -1, -2, -3, -0.0], dtype=torch.float64).repeat(2).to(src_dtype)
+    bigs = torch.tensor([big, -big, big, -big, 1.0], dtype=torch.float64).to(src_dtype)
+    bigx = torch.tensor([big, -big, -big, big, big], dtype=torch.float64).to(src_dtype)
+    k = 128 - int(np.frexp(big)[1])
+    return (
+        ("cross", va, vx, 1.0, 1.0),
+        ("cross-inf", va, vx, 1.0, inf),
+        ("cross-neg", va, vx, -0.0, -1.0),
+        ("f16sub", ia, ix, 2.0 ** -24, 2.0 ** -25),
+        ("bf16sub", ia, ix, 2.0 ** -133, 2.0 ** -134),
+        ("edge", ea, ex, 65504.0, 8.0),
+        ("edge-below", ea, ex, 65504.0, 7.995),
+        ("ovf", bigs, bigx, 2.0 ** k, 2.0 ** k),
+    )

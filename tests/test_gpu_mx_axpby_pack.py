@@ -94,8 +94,8 @@ def _run_shapes(codec, pair, plain):
         dev = _offset_view if view else torch.Tensor.cuda
         with _capped(cap):
             second = b.cuda() if plain else f["pack"](b.cuda())
-            # the siblings on operands of the same alignment: which groups
-            # they round to f16 in one step depends on it
+            # the siblings on operands of the same alignment (every path
+            # rounds an f16 the same way: test_gpu_combine_rounding.py)
             want = dev(torch.zeros(n, dtype=dst_dtype))
             (ops.axpby if plain else f["axpby"])(dev(a), dev(second.cpu()), 0.75, -1.25,
                                                  dst=want)
