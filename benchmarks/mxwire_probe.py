@@ -47,9 +47,9 @@ size and on a 1 GiB operand:
                                                         2+33/32 B read, 2+33/32 B written (bf16)
 
 and checks that both leave the same bytes in ``out`` and ``wire_out``.  For
-``mxfp4`` (17/32 B per element on each wire side) it also times the node whose
-two inputs are local: ``ops.axpby`` then ``ops.mx4_pack`` against
-``ops.mx4_axpby2_pack`` (the ``_plain`` keys).
+``mxfp4`` and ``mxfp6`` (17/32 and 25/32 B per element on each wire side) it
+also times the node whose two inputs are local: ``ops.axpby`` then
+``ops.mx4_pack`` against ``ops.mx4_axpby2_pack`` (the ``_plain`` keys).
 """
 import argparse
 import ctypes
@@ -158,12 +158,12 @@ def forward_mode(args) -> None:
         pre = _PREFIX[codec]
         pack, axpby, axpby_pack, axpby2_pack = (
             getattr(ops, f"{pre}_{k}") for k in ("pack", "axpby", "axpby_pack", "axpby2_pack"))
-        # the second operand: a received wire chunk, or (mxfp4 only, the
+        # the second operand: a received wire chunk, or (mxfp4 and mxfp6, the
         # node whose two inputs are local) a plain tensor
         for dtype, name in ((torch.bfloat16, "bf16"), (torch.float32, "f32")):
             es = 2 if dtype == torch.bfloat16 else 4
             for label, n in (("chunk", 8 << 20), ("1GiB", (1 << 30) // es)):
-                for plain in ((False, True) if codec == "mxfp4" else (False,)):
+                for plain in ((False, True) if codec in ("mxfp4", "mxfp6") else (False,)):
                     torch.manual_seed(5)
                     a = (torch.rand(n, device="cuda") + 0.5).to(dtype)
                     b = (torch.rand(n, device="cuda") + 0.5).to(dtype)
@@ -211,8 +211,8 @@ def forward_mode(args) -> None:
 
 _DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
 _PREFIX = {"mxfp8": "mx8", "mxint8": "mxi8", "mxfp4": "mx4", "mxfp6": "mx6"}
-# the codecs with a fused forwarding kernel (mxfp6 runs the two steps)
-_FORWARD = ("mxfp8", "mxint8", "mxfp4")
+# the codecs with a fused forwarding kernel
+_FORWARD = ("mxfp8", "mxint8", "mxfp4", "mxfp6")
 
 
 def _nbytes(codec: str, n: int) -> int:

@@ -37,8 +37,8 @@ kernel too (``lzy_amd.ops.mx4_axpby_pack`` / ``mx4_axpby2_pack``).
 
 The ``mx6_*`` functions are the three layers for MXFP6: 6-bit e2m3 codes,
 four in three bytes, ``uint8[25*nblk]`` (``mx6_nbytes``): the error of MXFP8
-at 24 % fewer link bytes.  A forwarding node on this wire is the combine
-kernel followed by the pack kernel (``mx6_axpby_pack`` / ``mx6_axpby2_pack``).
+at 24 % fewer link bytes.  A forwarding node on this wire is one kernel as
+well (``lzy_amd.ops.mx6_axpby_pack`` / ``mx6_axpby2_pack``).
 """
 from __future__ import annotations
 
@@ -550,46 +550,20 @@ def mx4_axpby2_pack(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
                        alpha, beta, dst, wire_out)
 
 
-def _mx6_then_pack(dst: torch.Tensor, wire_out: Optional[torch.Tensor]):
-    if _native(dst):
-        from lzy_amd import ops
-
-        return dst, ops.mx6_pack(dst, out=wire_out)
-    packed = mx6_pack_torch(dst)
-    if wire_out is None:
-        return dst, packed
-    wire_out.copy_(packed)
-    return dst, wire_out
-
-
 def mx6_axpby_pack(a: torch.Tensor, wire: torch.Tensor, alpha: float = 1.0,
                    beta: float = 1.0, dst: Optional[torch.Tensor] = None,
                    wire_out: Optional[torch.Tensor] = None):
-    """:func:`mx8_axpby_pack` for MXFP6 buffers, as its two steps on every
-    device: :func:`mx6_axpby`, then :func:`mx6_pack` of ``dst`` (there is no
-    fused kernel on this wire yet)."""
-    return _mx6_then_pack(mx6_axpby(a, wire, alpha, beta, dst), wire_out)
+    """:func:`mx8_axpby_pack` for MXFP6 buffers."""
+    return _axpby_pack("mx6_axpby_pack", mx6_axpby_torch, mx6_pack_torch, a, wire,
+                       alpha, beta, dst, wire_out)
 
 
 def mx6_axpby2_pack(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
                     beta: float = 1.0, dst: Optional[torch.Tensor] = None,
                     wire_out: Optional[torch.Tensor] = None):
-    """:func:`mx8_axpby2_pack` with an MXFP6 ``wire_out``, as its two steps:
-    the plain combine (``ops.axpby`` for device tensors), then the pack."""
-    if _native(a):
-        from lzy_amd import ops
-
-        return _mx6_then_pack(ops.axpby(a, b, alpha, beta, dst=dst), wire_out)
-    r = _axpby2_torch(a, b, alpha, beta, a.dtype if dst is None else dst.dtype)
-    if dst is None:
-        return _mx6_then_pack(r, wire_out)
-    if dst.shape != a.shape:
-        raise ValueError(
-            f"mx6_axpby2_pack: dst has shape {tuple(dst.shape)}, "
-            f"expected {tuple(a.shape)}"
-        )
-    dst.copy_(r)
-    return _mx6_then_pack(dst, wire_out)
+    """:func:`mx8_axpby2_pack` with an MXFP6 ``wire_out``."""
+    return _axpby_pack("mx6_axpby2_pack", _axpby2_torch, mx6_pack_torch, a, b,
+                       alpha, beta, dst, wire_out)
 
 
 # wire name (channel_wire_cast, stream_wire_cast, a plan's "wire") -> the

@@ -31,6 +31,8 @@ _MX4 = False  # ... and lz_mx4_pack / lz_mx4_unpack / lz_mx4_axpby (MXFP4)
 # ... and lz_mx4_axpby_pack / lz_mx4_axpby2_pack (the forwarding node on MXFP4)
 _MX4_AXPBY_PACK = False
 _MX6 = False  # ... and lz_mx6_pack / lz_mx6_unpack / lz_mx6_axpby (MXFP6)
+# ... and lz_mx6_axpby_pack / lz_mx6_axpby2_pack (the forwarding node on MXFP6)
+_MX6_AXPBY_PACK = False
 _SEGCOPY = False  # ... and lz_segcopy (the packed-bundle gather/scatter)
 # bytes per tile of the segmented copy — LZ_SEG_TILE in hipops.hip
 SEGCOPY_TILE = 16384
@@ -237,6 +239,15 @@ def _try_load() -> Optional[ctypes.CDLL]:
         _MX6 = True
     except AttributeError:
         _MX6 = False
+    global _MX6_AXPBY_PACK
+    try:
+        lib.lz_mx6_axpby_pack.restype = ctypes.c_int
+        lib.lz_mx6_axpby_pack.argtypes = lib.lz_mx4_axpby_pack.argtypes
+        lib.lz_mx6_axpby2_pack.restype = ctypes.c_int
+        lib.lz_mx6_axpby2_pack.argtypes = lib.lz_mx4_axpby2_pack.argtypes
+        _MX6_AXPBY_PACK = True
+    except AttributeError:
+        _MX6_AXPBY_PACK = False
     global _SEGCOPY
     try:
         lib.lz_segcopy.restype = ctypes.c_int
@@ -478,7 +489,8 @@ def _mx_entry(op: str):
         return getattr(_require_mx8(), "lz_" + op)
     lib = _require_native()
     if op.endswith("_pack") and "axpby" in op:
-        present = _MX4_AXPBY_PACK if op.startswith("mx4_") else _MX_AXPBY_PACK
+        present = _MX4_AXPBY_PACK if op.startswith("mx4_") else \
+            _MX6_AXPBY_PACK if op.startswith("mx6_") else _MX_AXPBY_PACK
     elif op.startswith("mx4_"):
         present = _MX4
     elif op.startswith("mx6_"):
@@ -763,6 +775,23 @@ def mx4_axpby2_pack(a, b, alpha: float = 1.0, beta: float = 1.0, dst=None,
     """:func:`mx8_axpby2_pack` with an MXFP4 ``wire_out``: ``dst`` is
     :func:`axpby`'s bit for bit, ``wire_out`` is ``mx4_pack(dst)``."""
     return _mx_axpby_pack("mx4_axpby2_pack", a, b, alpha, beta, dst, wire_out)
+
+
+def mx6_axpby_pack(a, wire, alpha: float = 1.0, beta: float = 1.0, dst=None,
+                   wire_out=None):
+    """:func:`mx6_axpby` and :func:`mx6_pack` of its result in one launch:
+    :func:`mx8_axpby_pack` for MXFP6.  ``wire`` and ``wire_out`` are
+    ``uint8[mx6_nbytes(a.numel())]``.  ``dst`` is ``mx6_axpby``'s bit for
+    bit (an f16 ``dst`` is the fp32 result rounded again, on every path),
+    ``wire_out`` byte for byte ``mx6_pack(dst)``."""
+    return _mx_axpby_pack("mx6_axpby_pack", a, wire, alpha, beta, dst, wire_out)
+
+
+def mx6_axpby2_pack(a, b, alpha: float = 1.0, beta: float = 1.0, dst=None,
+                    wire_out=None):
+    """:func:`mx8_axpby2_pack` with an MXFP6 ``wire_out``: ``dst`` is
+    :func:`axpby`'s bit for bit, ``wire_out`` is ``mx6_pack(dst)``."""
+    return _mx_axpby_pack("mx6_axpby2_pack", a, b, alpha, beta, dst, wire_out)
 
 
 def _mx_axpby_pack(op: str, a, second, alpha, beta, dst, wire_out):

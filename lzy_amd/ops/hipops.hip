@@ -2406,31 +2406,49 @@ mx6_pack_kernel(const T* __restrict__ src, uint8_t* __restrict__ dst, int64_t n)
     }
 }
 
-// decode one half and store it, or (COMBINE) its combine with the 16
-// elements fa of the accumulator: fmaf(a, alpha, x * beta), x in fp32.
-// FULL: all 16 elements lie in [0, n) and dst + e0 is 16 B-aligned.
-template <typename DstT, bool FULL, bool COMBINE>
-__device__ __forceinline__ void lz_mx6_dec_store(const LzVec12& pv, uint32_t b,
-                                                 const float (&fa)[16], DstT* dst,
-                                                 int64_t e0, int64_t n, float alpha,
-                                                 float beta) {
-    constexpr int V = 16;
-    float x[V];
+// the 12 payload bytes of half h; they exist for every h < 2*nblk
+template <bool ALIGNED>
+__device__ __forceinline__ LzVec12 lz_mx6_payload(const uint8_t* __restrict__ wire,
+                                                  int64_t h) {
+    LzVec12 pv;
+    if (ALIGNED) {
+        pv = *reinterpret_cast<const LzVec12*>(wire + h * 12);
+    } else {
+        pv.w[0] = pv.w[1] = pv.w[2] = 0;
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+            pv.w[k >> 2] |= (uint32_t)wire[h * 12 + k] << (8 * (k & 3));
+    }
+    return pv;
+}
+
+// the 16 codes of one half (three payload dwords) as fp32 values e2m3(q) / 64
+__device__ __forceinline__ void lz_mx6_codes16(const LzVec12& pv, float (&x)[16]) {
     lz_mx6_decode4(pv.w[0] & 0xffffffu, &x[0]);
     lz_mx6_decode4((pv.w[0] >> 24) | ((pv.w[1] & 0xffffu) << 8), &x[4]);
     lz_mx6_decode4((pv.w[1] >> 16) | ((pv.w[2] & 0xffu) << 16), &x[8]);
     lz_mx6_decode4(pv.w[2] >> 8, &x[12]);
-    const int e = (int)b - 121;
-    DstT y[V];
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-        float r = __builtin_ldexpf(x[k], e);
-        r = b == 0xffu ? __uint_as_float(0x7fc00000u) : r;
-        if constexpr (COMBINE)
-            y[k] = lz_narrow<DstT>(fmaf(fa[k], alpha, r * beta));
-        else
-            y[k] = lz_from_float<DstT>(r);
-    }
+}
+
+// one of them under its block's scale byte b: v_ldexp_f32 by b-121, NaN
+// under 0xff
+__device__ __forceinline__ float lz_mx6_scaled(float q, uint32_t b) {
+    const float r = __builtin_ldexpf(q, (int)b - 121);
+    return b == 0xffu ? __uint_as_float(0x7fc00000u) : r;
+}
+
+// the combine of this wire's kernels: fmaf(a, alpha, x * beta), x in fp32,
+// rounded to fp32 and then to DstT
+template <typename DstT>
+__device__ __forceinline__ DstT lz_mx6_combine(float a, float x, float alpha, float beta) {
+    return lz_narrow<DstT>(fmaf(a, alpha, x * beta));
+}
+
+// FULL: all 16 elements lie in [0, n) and dst + e0 is 16 B-aligned.
+template <typename DstT, bool FULL>
+__device__ __forceinline__ void lz_mx6_store16(const DstT (&y)[16], DstT* dst,
+                                               int64_t e0, int64_t n) {
+    constexpr int V = 16;
     if (FULL) {
         LzVec16 q[sizeof(DstT) * V / 16];
         __builtin_memcpy(q, y, sizeof(y));
@@ -2442,6 +2460,27 @@ __device__ __forceinline__ void lz_mx6_dec_store(const LzVec12& pv, uint32_t b,
         for (int k = 0; k < V; ++k)
             if (e0 + k < n) dst[e0 + k] = y[k];
     }
+}
+
+// decode one half and store it, or (COMBINE) its combine with the 16
+// elements fa of the accumulator.
+template <typename DstT, bool FULL, bool COMBINE>
+__device__ __forceinline__ void lz_mx6_dec_store(const LzVec12& pv, uint32_t b,
+                                                 const float (&fa)[16], DstT* dst,
+                                                 int64_t e0, int64_t n, float alpha,
+                                                 float beta) {
+    float x[16];
+    lz_mx6_codes16(pv, x);
+    DstT y[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const float r = lz_mx6_scaled(x[k], b);
+        if constexpr (COMBINE)
+            y[k] = lz_mx6_combine<DstT>(fa[k], r, alpha, beta);
+        else
+            y[k] = lz_from_float<DstT>(r);
+    }
+    lz_mx6_store16<DstT, FULL>(y, dst, e0, n);
 }
 
 // mx6_unpack (COMBINE false: a unused) and mx6_axpby share this kernel: three
@@ -2463,16 +2502,7 @@ mx6_decode_kernel(const SrcT* a, const uint8_t* __restrict__ wire, DstT* dst, in
          h += stride) {
         const int64_t e0 = h * 16;
         if (e0 >= n) continue;  // padded second half of the last block
-        // the 12 payload bytes of half h exist for every h < 2*nblk
-        LzVec12 pv;
-        if (ALIGNED) {
-            pv = *reinterpret_cast<const LzVec12*>(wire + h * 12);
-        } else {
-            pv.w[0] = pv.w[1] = pv.w[2] = 0;
-#pragma unroll
-            for (int k = 0; k < 12; ++k)
-                pv.w[k >> 2] |= (uint32_t)wire[h * 12 + k] << (8 * (k & 3));
-        }
+        const LzVec12 pv = lz_mx6_payload<ALIGNED>(wire, h);
         const uint32_t b = scales[h >> 1];
         float fa[16] = {};
         if (ALIGNED && e0 + 16 <= n) {
@@ -2592,6 +2622,188 @@ extern "C" hipError_t lz_mx6_axpby(const void* a, int a_dtype, const void* wire_
 #undef LZ_MX6A_SRC
 #undef LZ_MX6A_DST
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// mx6_axpby_pack / mx6_axpby2_pack: the step of a merge-tree node that
+// forwards on the MXFP6 wire (docs/mxwire.md, "MXFP6", Forwarding nodes), in
+// one pass:
+//   dst      = cast(alpha*a + beta*x)   x = decode(wire_in), or a plain b
+//   wire_out = mx6_pack(dst)
+// lz_mx6_axpby followed by lz_mx6_pack of its result moves 7.56 B/element of
+// bf16 through HBM in two launches; here the value is encoded while it is
+// still in registers: 5.56 B/element (2 + 25/32 read, 2 + 25/32 written).
+//
+// dst is lz_mx6_axpby's (axpby_kernel's) value bit for bit and wire_out byte
+// for byte what lz_mx6_pack makes of that dst: lz_mx6_emit is handed the value
+// already rounded to DstT and widened back to fp32, +0.0 at positions >= n
+// whatever the padding codes and the scale byte of wire_in decode to.
+//
+// Work split of this section: a lane owns one half per trip (three payload
+// dwords in, 16 elements, three payload dwords out), an aligned lane pair a
+// block, a wave 32 blocks.  Decode and combine are lz_mx6_axpby's own
+// (lz_mx6_codes16, lz_mx6_scaled, lz_mx6_combine) and stay inside the lane; only
+// lz_mx6_emit crosses lanes (one DPP step for the block's amax and NaN key,
+// three row shifts for the scale bytes).  So the loop is mx6_pack_kernel's:
+// h0 and every branch on it are wave-uniform, and a lane whose half lies past
+// the tensor loads nothing, stores nothing to dst and goes through the encoder
+// with zeros -- the padded second half of the last block gets its 12 zero
+// payload bytes that way.  On the unguarded path the payload dwordx3, the
+// scale byte and the 16 B loads of a (and b) issue before any is consumed.
+//
+// dst may be a (a lane reads its 16 elements before it writes them);
+// wire_out must not overlap any other argument.
+// ---------------------------------------------------------------------------
+
+// the second operand of one half, loaded and not yet consumed: the payload
+// and scale byte of a wire (WIRE), or 16 plain elements as fp32
+struct LzMx6Second {
+    LzVec12 pv;
+    uint32_t b;
+    float f[16];
+};
+
+template <typename SrcT, bool WIRE, bool ALIGNED, bool FULL>
+__device__ __forceinline__ void lz_mx6f_fetch(const void* src2,
+                                              const uint8_t* __restrict__ scales_in,
+                                              int64_t h, int64_t n, LzMx6Second& s) {
+    if constexpr (WIRE) {
+        s.pv = lz_mx6_payload<ALIGNED>(static_cast<const uint8_t*>(src2), h);
+        s.b = scales_in[h >> 1];
+    } else {
+        lz_mx6_load<SrcT, FULL>(static_cast<const SrcT*>(src2), h * 16, n, s.f);
+    }
+}
+
+// combine one half, store it to dst and leave in r what the encoder sees:
+// the stored value as fp32, +0.0 at positions >= n.  FULL: all 16 elements
+// lie inside [0, n) and dst + e0 is 16 B-aligned.
+template <typename DstT, bool WIRE, bool FULL>
+__device__ __forceinline__ void lz_mx6f_combine(const float (&fa)[16],
+                                                const LzMx6Second& s, DstT* dst,
+                                                int64_t e0, int64_t n, float alpha,
+                                                float beta, float (&r)[16]) {
+    float x[16];
+    if constexpr (WIRE) lz_mx6_codes16(s.pv, x);
+    DstT y[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const float v = WIRE ? lz_mx6_scaled(x[k], s.b) : s.f[k];
+        y[k] = lz_mx6_combine<DstT>(fa[k], v, alpha, beta);
+        r[k] = (FULL || e0 + k < n) ? lz_to_float<DstT>(y[k]) : 0.f;
+    }
+    lz_mx6_store16<DstT, FULL>(y, dst, e0, n);
+}
+
+template <typename SrcT, typename DstT, bool WIRE, bool ALIGNED>
+__global__ void __launch_bounds__(LZ_BLOCK) LZ_NO_PK_F32
+mx6_axpby_pack_kernel(const SrcT* a, const void* src2, DstT* dst,
+                      uint8_t* __restrict__ wire_out, int64_t n, float alpha,
+                      float beta) {
+    const int64_t nblk = (n + 31) >> 5;
+    const int64_t nhalves = nblk * 2;
+    const uint8_t* __restrict__ scales_in =
+        WIRE ? static_cast<const uint8_t*>(src2) + nblk * 24 : nullptr;
+    uint8_t* __restrict__ scales_out = wire_out + nblk * 24;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+
+    for (int64_t h0 = (int64_t)blockIdx.x * blockDim.x + wave * 64; h0 < nhalves;
+         h0 += stride) {
+        const int64_t h = h0 + lane, e0 = h * 16;
+        LzMx6Second s;
+        float fa[16], r[16];
+        if (ALIGNED && (h0 + 64) * 16 <= n) {  // the halves of all 64 lanes whole
+            lz_mx6f_fetch<SrcT, WIRE, true, true>(src2, scales_in, h, n, s);
+            lz_mx6_load<SrcT, true>(a, e0, n, fa);
+            // keeps every load above the first wait
+            __builtin_amdgcn_sched_barrier(0);
+            lz_mx6f_combine<DstT, WIRE, true>(fa, s, dst, e0, n, alpha, beta, r);
+            lz_mx6_emit<true, true>(r, h, lane, nhalves, nblk, wire_out, scales_out);
+        } else {
+            // the branches are per lane and close before the cross-lane encode
+#pragma unroll
+            for (int k = 0; k < 16; ++k) r[k] = 0.f;
+            if (e0 < n) {
+                if (ALIGNED && e0 + 16 <= n) {
+                    lz_mx6f_fetch<SrcT, WIRE, ALIGNED, true>(src2, scales_in, h, n, s);
+                    lz_mx6_load<SrcT, true>(a, e0, n, fa);
+                    lz_mx6f_combine<DstT, WIRE, true>(fa, s, dst, e0, n, alpha, beta, r);
+                } else {
+                    lz_mx6f_fetch<SrcT, WIRE, ALIGNED, false>(src2, scales_in, h, n, s);
+                    lz_mx6_load<SrcT, false>(a, e0, n, fa);
+                    lz_mx6f_combine<DstT, WIRE, false>(fa, s, dst, e0, n, alpha, beta, r);
+                }
+            }
+            lz_mx6_emit<ALIGNED, false>(r, h, lane, nhalves, nblk, wire_out, scales_out);
+        }
+    }
+}
+
+// a, dst: n elements of a_dtype / dst_dtype (both f32/f16/bf16); src2: the
+// MXFP6 wire of n elements (WIRE) or n more elements of a_dtype; wire_out:
+// 25*ceil(n/32) bytes.  dst == a is allowed; wire_out overlaps nothing.
+template <bool WIRE>
+static hipError_t lz_mx6_axpby_pack_launch(const void* a, int a_dtype, const void* src2,
+                                           void* dst, int dst_dtype, void* wire_out,
+                                           int64_t n, float alpha, float beta,
+                                           void* stream) {
+    if (!lz_mx_float_dtype(a_dtype) || !lz_mx_float_dtype(dst_dtype) || n < 0)
+        return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipStream_t s = (hipStream_t)stream;
+    const int blocks = lz_mx6_grid(n);
+    const bool aligned = (((uintptr_t)a & 15) == 0) && (((uintptr_t)dst & 15) == 0) &&
+                         (((uintptr_t)src2 & (WIRE ? 3 : 15)) == 0) &&
+                         (((uintptr_t)wire_out & 3) == 0);
+#define LZ_MX6F_LAUNCH(AL)                                                      \
+    hipLaunchKernelGGL((mx6_axpby_pack_kernel<S, D, WIRE, AL>), dim3(blocks),   \
+                       dim3(LZ_BLOCK), 0, s, (const S*)a, src2, (D*)dst,        \
+                       (uint8_t*)wire_out, n, alpha, beta)
+#define LZ_MX6F_DST(SrcT, code, DstT)                                           \
+    case code: {                                                                \
+        using S = SrcT;                                                         \
+        using D = DstT;                                                         \
+        if (aligned) LZ_MX6F_LAUNCH(true);                                      \
+        else LZ_MX6F_LAUNCH(false);                                             \
+        break;                                                                  \
+    }
+#define LZ_MX6F_SRC(scode, SrcT)                                                \
+    case scode:                                                                 \
+        switch (dst_dtype) {                                                    \
+            LZ_MX6F_DST(SrcT, LZ_F32, float)                                    \
+            LZ_MX6F_DST(SrcT, LZ_F16, __half)                                   \
+            LZ_MX6F_DST(SrcT, LZ_BF16, __hip_bfloat16)                          \
+            default: return hipErrorInvalidValue;                               \
+        }                                                                       \
+        break;
+    switch (a_dtype) {
+        LZ_MX6F_SRC(LZ_F32, float)
+        LZ_MX6F_SRC(LZ_F16, __half)
+        LZ_MX6F_SRC(LZ_BF16, __hip_bfloat16)
+        default: return hipErrorInvalidValue;
+    }
+#undef LZ_MX6F_SRC
+#undef LZ_MX6F_DST
+#undef LZ_MX6F_LAUNCH
+    return hipGetLastError();
+}
+
+extern "C" hipError_t lz_mx6_axpby_pack(const void* a, int a_dtype, const void* wire_in,
+                                        void* dst, int dst_dtype, void* wire_out,
+                                        int64_t n, float alpha, float beta,
+                                        void* stream) {
+    return lz_mx6_axpby_pack_launch<true>(a, a_dtype, wire_in, dst, dst_dtype, wire_out,
+                                          n, alpha, beta, stream);
+}
+
+extern "C" hipError_t lz_mx6_axpby2_pack(const void* a, const void* b, int src_dtype,
+                                         void* dst, int dst_dtype, void* wire_out,
+                                         int64_t n, float alpha, float beta,
+                                         void* stream) {
+    return lz_mx6_axpby_pack_launch<false>(a, src_dtype, b, dst, dst_dtype, wire_out, n,
+                                           alpha, beta, stream);
 }
 
 // ---------------------------------------------------------------------------
